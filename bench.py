@@ -10,7 +10,7 @@ by all ranks / max-over-ranks frame time.  --ranked takes that RCCL path even at
 1-rank communicator).  RTG_BENCH_REHEARSE=1 rehearses the N-rank path on one GPU (every rank
 on cuda:0, gloo gather through host memory); its numbers are not a scaling measurement.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0): main() says what a plain run does.  Extra objects (--full only):
   roofline     the dominant kernel (k_trace, closest hit) against the ceiling that binds it, VALU
                issue (MI355X_MICROARCH.md: 256 CUs x 4 SIMD-32, one wave64 VALU instruction per 2
                cycles at 2.4 GHz = 1228.8 G wave-instructions/s), from the committed PMC counters
@@ -397,7 +397,13 @@ def main():
                     help="rows of the CPU baseline sample (0: about 10-30 s of CPU work for the workload)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads for cpu_baseline; 0 = every CPU this job is granted (host_cpu_info)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline and its parity rows")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: end-to-end times of a fresh "
+                         "scene, frames copied to the host, per-kernel rooflines, a second scene creation, the "
+                         "CPU baseline + parity rows, and (N > 1 / --ranked) the gathered frame against rank 0's own")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's frame to DIR/frame.npy (float32)")
     ap.add_argument("--ranked", action="store_true",
                     help="render through rtg_render_ranked (RCCL shard + gather) even with one rank")
     ap.add_argument("--tlas", choices=["auto", "off", "on"], default="auto",
@@ -409,6 +415,12 @@ def main():
                     help="N > 1: bound on every wait for a peer rank (process group set-up, id exchange, "
                          "librtg's RCCL set-up / failure agreement / gather); a dead peer is an error, not a hang")
     args = ap.parse_args()
+    # A plain run sets up, warms up, times --steps frames and prints the headline fields (metric, value,
+    # unit, ms_per_step, ...).  --dump-outputs DIR then writes the frame the last timed step left, what a
+    # caller of the timed path receives, to DIR/frame.npy (float32, ny x nx x 3): the scenes are seeded, so
+    # two builds can be compared output for output.  --full adds everything else the benchmark measures,
+    # each in runs of its own outside the timed loop (the module docstring's extra objects, the end-to-end
+    # times of a fresh scene and the frames copied to the host).
     # stdout carries exactly the one JSON line: libraries that print banners there (RCCL's
     # "RCCL version ..." at communicator init) are sent to stderr with everything else
     json_out = os.fdopen(os.dup(1), "w")
@@ -463,7 +475,7 @@ def main():
     cam = scene.cameras[0]
     pt = cam.integrator == rtg_abi.INTEGRATOR_PATH
     frame = torch.zeros((cam.ny, cam.nx, 3), dtype=torch.float32, device=f"cuda:{local}")
-    host = torch.empty((cam.ny, cam.nx, 3), dtype=torch.float32, pin_memory=True)
+    host = torch.empty((cam.ny, cam.nx, 3), dtype=torch.float32, pin_memory=True) if args.full else None
     stream = torch.cuda.current_stream().cuda_stream
     comm = None
     part = None
@@ -506,16 +518,18 @@ def main():
         single(buf, collect_timing=1, streams=1)
         return st_stats, single(buf, collect_timing=1, streams=1)
 
-    # one frame to the host right after the upload: the end-to-end time of a fresh scene
-    t0 = time.perf_counter()
-    step()
-    if rank == 0:
-        host.copy_(frame, non_blocking=True)
-    torch.cuda.synchronize()
-    first_frame_ms = (time.perf_counter() - t0) * 1e3
+    first_frame_ms = 0.0
     st_stats = st_roof = None
-    if not sharded:
-        st_stats, st_roof = roofline_frames(frame)
+    if args.full:
+        # one frame to the host right after the upload: the end-to-end time of a fresh scene
+        t0 = time.perf_counter()
+        step()
+        if rank == 0:
+            host.copy_(frame, non_blocking=True)
+        torch.cuda.synchronize()
+        first_frame_ms = (time.perf_counter() - t0) * 1e3
+        if not sharded:
+            st_stats, st_roof = roofline_frames(frame)
     for _ in range(args.warmup):
         step()
 
@@ -558,13 +572,17 @@ def main():
         return elapsed, rays, st
 
     elapsed, rays, st = timed(False)
-    elapsed_h, _, _ = timed(True)
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step (N > 1: the gathered frame on rank 0)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"), frame.cpu().numpy())
+    elapsed_h = timed(True)[0] if args.full else None
     ms_per_step = elapsed * 1e3 / args.steps
     value = rays / elapsed / 1e6
     rays_frame = rays // max(args.steps, 1)
 
     multi = None
-    if sharded and rank == 0:
+    if args.full and sharded and rank == 0:
         # rank 0 alone: the full frame on its own device vs the gathered frame (bit for bit), then
         # its single-device roofline frames (same kernels and counters as the N = 1 line)
         full = torch.zeros_like(frame)
@@ -596,7 +614,8 @@ def main():
     if dist is not None:
         dist.barrier()
 
-    if rank == 0:
+    def full_fields() -> dict:
+        """--full, rank 0: what the line holds beyond the headline fields."""
         # the same scene created again in this process (outside every timed region): the first
         # rtg_scene_create also pays the HIP runtime's one-time first-use set-up, ~100-150 ms for the
         # first launch / copy of a process (scripts/micro/init_probe.hip, profiles/history/r4m_init_probe.txt)
@@ -625,6 +644,24 @@ def main():
                                                args.cpu_threads or host_cpu_info()["cpus_granted"])
             parity = compare_rows(host.numpy()[rows[0]:rows[1]], ref_rows, rows)
             log(f"[rank 0] parity rows {rows}: linf={parity['linf']} differing={parity['differing']}")
+        more = {"ms_per_frame_to_host": round(elapsed_h * 1e3 / args.steps, 2),
+                "end_to_end_ms": {"runtime_init": round(runtime_init_ms, 1),
+                                  "scene_create": round(create_ms, 1), "first_frame_to_host": round(first_frame_ms, 1),
+                                  "total": round(runtime_init_ms + create_ms + first_frame_ms, 1),
+                                  "scene_create_phases": create_phases(r.build_stats(), create_ms),
+                                  "scene_create_again": again,
+                                  "note": "runtime_init = the process's first kernel launch (torch.zeros, the HIP "
+                                          "runtime's one-time set-up); Renderer(scene) = the Python host's descriptor "
+                                          "(desc_python) + rtg_scene_create (library phases), then the first frame incl. "
+                                          "its D2H copy"},
+                "kernel_ms_rank0_streams1": {k: round(st_roof[f"{k}_ms"], 2)
+                                             for k in ("trace", "shade", "shadow", "resolve", "accumulate")},
+                "roofline": roof, "cpu_baseline": cpu, "parity": parity, "multi": multi}
+        if cpu_note:
+            more["cpu_baseline_note"] = cpu_note
+        return more
+
+    if rank == 0:
         if world == 1 and comm is None:
             par = "single GPU"
         elif rehearse:
@@ -639,22 +676,10 @@ def main():
                            "parallelism": par, "tlas": args.tlas, "tlas_nodes": r.build_stats()["tlas_nodes"]},
                 "rays_per_frame": rays_frame,
                 "primary_msamples_s": round(cam.nx * cam.ny * cam.num_samples / (ms_per_step * 1e-3) / 1e6, 1),
-                "ms_per_frame_to_host": round(elapsed_h * 1e3 / args.steps, 2),
-                "end_to_end_ms": {"runtime_init": round(runtime_init_ms, 1),
-                                  "scene_create": round(create_ms, 1), "first_frame_to_host": round(first_frame_ms, 1),
-                                  "total": round(runtime_init_ms + create_ms + first_frame_ms, 1),
-                                  "scene_create_phases": create_phases(r.build_stats(), create_ms),
-                                  "scene_create_again": again,
-                                  "note": "runtime_init = the process's first kernel launch (torch.zeros, the HIP "
-                                          "runtime's one-time set-up); Renderer(scene) = the Python host's descriptor "
-                                          "(desc_python) + rtg_scene_create (library phases), then the first frame incl. "
-                                          "its D2H copy"},
                 "rays_rank0": {k: st[k] for k in ("primary_rays", "secondary_rays", "shadow_rays")},
-                "kernel_ms_rank0_streams1": {k: round(st_roof[f"{k}_ms"], 2)
-                                             for k in ("trace", "shade", "shadow", "resolve", "accumulate")},
-                "roofline": roof, "cpu_baseline": cpu, "parity": parity, "multi": multi}
-        if cpu_note:
-            line["cpu_baseline_note"] = cpu_note
+                "full": args.full}
+        if args.full:
+            line.update(full_fields())
         print(json.dumps(line), file=json_out, flush=True)
     if comm is not None:
         comm.close()

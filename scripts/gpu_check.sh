@@ -17,7 +17,7 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 [ -n "$SKIP_BENCH" ] && { echo done; exit 0; }
 for wl in ${WLS:-dragon1m}; do
-  timeout -k 10 600 python3 bench.py --workload $wl $BENCH_ARGS > $D/bench_$wl.json 2> $D/bench_$wl.err \
+  timeout -k 10 600 python3 bench.py --full --workload $wl $BENCH_ARGS > $D/bench_$wl.json 2> $D/bench_$wl.err \
     || { tail -20 $D/bench_$wl.err; exit 1; }
   python3 -c "import json,sys; d=json.load(open('$D/bench_$wl.json')); print('$wl', d['ms_per_step'], 'ms', d['value'], 'Mray/s', 'parity', (d.get('parity') or {}).get('differing'), 'k_ms', d['kernel_ms_rank0_streams1'])"
 done

@@ -5,6 +5,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 P=${1:-r3c}
+EXTRA_ARGS="--full $EXTRA_ARGS"     # every bench line below carries the rooflines, frame HBM and parity rows
 for wl in ${WLS:-dragon1m cornell cornell_pt bunny}; do
   echo "=== $wl"
   SKIP_TESTS=1 BENCH_ARGS="--workload $wl $EXTRA_ARGS" bash scripts/gpu_round.sh ${P}_$wl > gpurun_out/prof_${P}_$wl.txt 2>&1 \

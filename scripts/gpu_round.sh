@@ -14,11 +14,11 @@ if [ -z "$SKIP_TESTS" ]; then
     || { tail -40 $D/gputest.log; exit 1; }
   tail -2 $D/gputest.log
 fi
-timeout -k 10 600 python3 bench.py $BENCH_ARGS > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full $BENCH_ARGS > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
 cat $D/bench.json
 # kernel trace: passes serialised (--streams 1) so every launch is timed alone
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $D/kt -o kt --output-format csv -- \
-    python3 bench.py --no-cpu --streams 1 $BENCH_ARGS > $D/bench_kt.json 2> $D/bench_kt.err || { tail -20 $D/bench_kt.err; exit 1; }
+    python3 bench.py --full --no-cpu --streams 1 $BENCH_ARGS > $D/bench_kt.json 2> $D/bench_kt.err || { tail -20 $D/bench_kt.err; exit 1; }
 echo "kernel trace done"
 # PMC passes (one counter set per run: at most 8 SQ, 4 TCC, 4 TCP, 2 GRBM counters)
 i=0
@@ -28,7 +28,7 @@ for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS S
            "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   timeout -s KILL 300 rocprofv3 --pmc $set --kernel-trace -d $D/p$i -o p$i --output-format csv -- \
-      python3 bench.py --steps 1 --warmup 0 --no-cpu --streams 1 $BENCH_ARGS > $D/p$i.out 2> $D/p$i.err \
+      python3 bench.py --full --steps 1 --warmup 0 --no-cpu --streams 1 $BENCH_ARGS > $D/p$i.out 2> $D/p$i.err \
       || { echo "pmc pass $i failed"; tail -5 $D/p$i.err; exit 1; }
   echo "pmc pass $i done"
 done

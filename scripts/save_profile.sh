@@ -20,5 +20,5 @@ if ks:
 PY
 cp $D/kt/kt_kernel_stats.csv profiles/${TAG}_kernel_stats.csv
 python3 scripts/pmc_traffic.py $D profiles/${TAG}_pmc_traffic.json \
-    "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-cpu"
+    "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu"
 cp profiles/${TAG}_pmc_traffic.json profiles/traffic_current.json

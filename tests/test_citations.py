@@ -4,46 +4,37 @@ symbol (`Triangle::bvhIntersect (src/Shape.cpp:297-345)`, `/* PointLight::BasicS
 Light.cpp:238-250 */`, `// ComputeBoundingBox BVH.cpp:268-283`) that symbol must appear in the
 cited lines.  A bare `:a-b` continues the file named last before it in the same source file.
 
-Runs only where the reference checkout exists (this container); the GPU box has none."""
+The reference is not part of this repository: its files' line counts and the lines each of its
+function names appears on are recorded in tests/golden/reference_index.json
+(tests/golden/make_reference_index.py writes it from a reference checkout)."""
+import json
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
+INDEX = os.path.join(ROOT, "tests", "golden", "reference_index.json")
 FILES = (r"(?:BVH|Scene|Shape|Helper|Light|Camera|Texture|Perlin|Ray|Image|Parser|defs|Material|Instance|"
          r"Transformation|BTNode|main|tinyexr|tinyxml2|happly)\.(?:cpp|h)")
 CITE = re.compile(r"(?:src/)?(" + FILES + r")?:(\d+(?:-\d+)?(?:,\s*\d+(?:-\d+)?)*)")
 SKIP_DIRS = {".git", "gpurun_out", "profiles", "__pycache__", "build", ".pytest_cache", ".hypothesis"}
 # documents written by others (the survey, the judge's review) are not this repository's claims
-SKIP_FILES = {"SURVEY.md", "VERDICT.md", "ADVICE.md", "PAPERS.md", "SNIPPETS.md", "test_citations.py"}
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout absent (GPU box)")
-
-
-def _ref_lines(name, cache={}):
-    if name not in cache:
-        with open(os.path.join(REF, name), errors="replace") as f:
-            cache[name] = f.read().split("\n")
-    return cache[name]
+SKIP_FILES = {"SURVEY.md", "VERDICT.md", "ADVICE.md", "PAPERS.md", "SNIPPETS.md", "test_citations.py",
+              "make_reference_index.py"}
 
 
-def _ref_symbols(cache={}):
+def _index(cache={}):
+    if not cache:
+        with open(INDEX) as f:
+            cache.update(json.load(f))
+    return cache
+
+
+def _ref_symbols():
     """Names of the functions the reference defines (a definition line: a name, a parameter list
     and no `;`), minus class names (constructors are matched only when written `Class::Class`)."""
-    if not cache:
-        defs, classes = set(), set()
-        for f in os.listdir(REF):
-            if not f.endswith((".cpp", ".h")) or f.startswith(("tinyexr", "tinyxml2", "happly")):
-                continue
-            for line in _ref_lines(f):
-                m = re.match(r"^\s*(?:[\w:<>\*&]+\s+)*?(?:\w+::)?([A-Za-z_]\w*)\s*\([^;]*$", line)
-                if m and not re.match(r"^\s*(if|for|while|switch|return|else)\b", line):
-                    defs.add(m.group(1))
-                classes |= set(re.findall(r"(?:class|struct)\s+([A-Za-z_]\w*)", line))
-        cache["defs"], cache["classes"] = defs, classes
-    return cache["defs"], cache["classes"]
+    return set(_index()["defs"]), set(_index()["classes"])
 
 
 def _ranges(spec):
@@ -79,7 +70,7 @@ def citations():
     return found
 
 
-CITATIONS = citations() if os.path.isdir(REF) else []
+CITATIONS = citations()
 
 
 def test_there_are_citations():
@@ -89,9 +80,9 @@ def test_there_are_citations():
 @pytest.mark.parametrize("where,ln,ref,spec,before", CITATIONS,
                          ids=[f"{w}:{n}->{f}:{s}" for w, n, f, s, _ in CITATIONS])
 def test_citation_resolves(where, ln, ref, spec, before):
-    assert os.path.exists(os.path.join(REF, ref)), f"{where}:{ln}: no reference file {ref}"
-    lines = _ref_lines(ref)
-    n = len(lines) - (1 if lines and lines[-1] == "" else 0)
+    files = _index()["files"]
+    assert ref in files, f"{where}:{ln}: no reference file {ref}"
+    n = files[ref]["lines"]
     rs = _ranges(spec)
     for a, b in rs:
         assert 1 <= a <= b <= n, f"{where}:{ln}: {ref}:{a}-{b} outside the file ({n} lines)"
@@ -107,6 +98,6 @@ def test_citation_resolves(where, ln, ref, spec, before):
     if not cand:
         return
     sym = cand[-1]
-    body = "\n".join("\n".join(lines[a - 1:b]) for a, b in rs)
-    assert re.search(r"\b" + re.escape(sym) + r"\b", body), \
+    named_on = files[ref]["symbols"].get(sym, [])
+    assert any(a <= x <= b for x in named_on for a, b in rs), \
         f"{where}:{ln}: `{sym}` does not appear in {ref}:{spec}"
