@@ -1926,7 +1926,7 @@ DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const P
     // (the point store below; decided here for the whole wave -- a superset -- so that neither the
     // origin nor a per-lane flag is live across the shading)
     const bool o_far = __ballot(!(fabsf(o.x) < 1e17f && fabsf(o.y) < 1e17f && fabsf(o.z) < 1e17f)) != 0ull;
-    int nchild = 0;
+    // (child rays: has0 / has1 below)
     QRay c0r, c1r;
     RayMeta c0m, c1m;
     bool has0 = false, has1 = false;
@@ -2071,42 +2071,42 @@ DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const P
             }
         }
         if (basic) nd.kind |= 0x100;
-        nchild = (has0 ? 1 : 0) + (has1 ? 1 : 0);
+        // (has0: a refracted child, has1: a reflected one)
     }
     // Compaction of the next level's rays and of the shadow-query list (entries
     // i * nLights + li, light-major within a wave): ballot prefixes inside each wave, wave
     // totals combined in LDS, ONE 64-bit atomic per block on the level's queue counter
     // (low word: rays, high word: shadow entries).  Same-address atomics serialise at the L2
     // (~11 ns each), so they are kept to one per block.
-    __shared__ unsigned s_wc[BLOCK / 64], s_ws[BLOCK / 64];
-    __shared__ unsigned long long s_base;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // Round 7: the positions come from queue_slots (rtg_internal.h), which also orders the children.
+    // Each lane's refracted and reflected child used to sit side by side in the next level's queue, so
+    // under a glass surface every wave of that level was half rays inside the sphere (they can only
+    // hit it again) and half rays outside it (floor, mesh, sky), and ran both halves' work.  With
+    // SceneView::child_split the block queues all its refracted children, then all its reflected ones:
+    // a 512-ray block of glass hits gives 8 waves of inside rays and 8 of outside rays.  Only queue
+    // positions change -- a node finds its children by index (NodePlanes::link), random numbers are
+    // keyed by pixel, sample and path -- so every result is the same bit for bit.  Dragon: k_trace's
+    // walk lane slots 798 M -> 742 M per frame, the frame 27.0 -> 25.4 ms; spheres 28.2 -> 26.4 ms
+    // (profiles/ab_iso_sphere.jsonl).  child_split 0 (RTG_CHILD_SPLIT=0 at
+    // scene creation): the pairs as before, a data switch for A/B runs and the test.
+    // (The prefix arithmetic is unchanged: ballot prefixes per wave, wave totals combined in LDS, one
+    // 64-bit atomic per block; split, thread 0 runs a second prefix over the waves' reflected counts,
+    // which start where the refracted ones end, and every position follows from has0 /
+    // has1.)
     const unsigned long long lt = __lanemask_lt();
-    const unsigned long long m1 = __ballot(nchild >= 1), m2 = __ballot(nchild >= 2);
-    const unsigned coff = __popcll(m1 & lt) + __popcll(m2 & lt);
     unsigned stot = 0;
     for (int li = 0; li < sv.num_lights; li++) stot += __popcll(__ballot((smask >> li) & 1ull));
-    if (lane == 0) { s_wc[w] = __popcll(m1) + __popcll(m2); s_ws[w] = stot; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned c = 0, sh = 0;
-        for (int k = 0; k < BLOCK / 64; k++) {
-            const unsigned a = s_wc[k], b = s_ws[k];
-            s_wc[k] = c; s_ws[k] = sh;
-            c += a; sh += b;
-        }
-        s_base = (c | sh) ? atomicAdd(qcount, ((unsigned long long)sh << 32) | c) : 0ull;
-    }
-    __syncthreads();
-    int idx = (int)((unsigned)s_base + s_wc[w] + coff);
+    int idx, idx1;          // queue positions of this lane's refracted / reflected child
+    unsigned sb;            // this wave's first position in the shadow-query list
+    queue_slots<BLOCK>(sv.child_split != 0, has0, has1, stot, qcount, idx, idx1, sb);
     if (i < n) {
         auto put_ray = [&](int k, const QRay& rr, const RayMeta& mm) {
             store_ray(next_rays, k, rr.o, rr.d, rr.time);
             if (!sv.meta_free) next_meta[k] = mm;
             if (lv_out) lv_out[k] = (unsigned char)(level + 1);
         };
-        if (has0) { put_ray(idx, c0r, c0m); nd.child0 = idx; idx++; }
-        if (has1) { put_ray(idx, c1r, c1m); nd.child1 = idx; }
+        if (has0) { put_ray(idx, c0r, c0m); nd.child0 = idx; }
+        if (has1) { put_ray(idx1, c1r, c1m); nd.child1 = idx1; }
         // kNodeFar: a hit point whose distance to another could overflow (or is not finite) --
         // k_resolve then reads it even for Beer's law with zero absorption
         const bool far = hit && !(fabsf(nd.px) < 1e18f && fabsf(nd.py) < 1e18f && fabsf(nd.pz) < 1e18f);
@@ -2124,7 +2124,7 @@ DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const P
             nodes.pnt[i] = make_float4(nd.px, nd.py, nd.pz, nd.F);
         if ((nd.kind & 0xFF) != NK_FINAL) nodes.link[i] = make_int4(nd.child0, nd.child1, nd.material, 0);
     }
-    unsigned sb = (unsigned)(s_base >> 32) + s_ws[w];
+    // (sb: from queue_slots, above)
     for (int li = 0; li < sv.num_lights; li++) {
         const bool need = (smask >> li) & 1ull;
         const unsigned long long m = __ballot(need);

@@ -2296,7 +2296,7 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
     sv.num_gtris = s->num_gtris;
     sv.num_gents = s->num_gents;
     for (int z = 0; z < 3; z++) sv.tlas_k[z] = s->tlas_k[z];
-    sv.pt_flags = 0;
+    sv.pt_flags = 0; sv.child_split = child_split_default();   // (RTG_CHILD_SPLIT, rtg_internal.h)
     sv.max_depth = d->max_recursion_depth;
     sv.shadow_eps = d->shadow_ray_eps;
     sv.int_eps = d->intersection_test_eps;
@@ -3390,3 +3390,12 @@ int32_t rtg_scene_vertex_normals(const rtg_scene* s, float* normals) {
 }
 
 }  // extern "C"
+
+namespace rtg {
+// RTG_CHILD_SPLIT=0: k_shade queues each ray's two children side by side, as before round 7
+// (SceneView::child_split, queue_slots in rtg_internal.h); anything else, or unset: the split.
+int child_split_default() {
+    const char* e = getenv("RTG_CHILD_SPLIT");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+}  // namespace rtg

@@ -180,7 +180,7 @@ struct SceneView {
     const float* vnormals;         // xyz
     const float* texcoords;        // uv
     int num_texcoords;
-    const MaterialDev* materials; int num_materials;
+    const MaterialDev* materials; int num_materials; int child_split;   // child_split: queue_slots (below; in former padding)
     const TextureDev* textures; int num_textures;
     const float* texels;
     const LightDev* lights; int num_lights;
@@ -589,5 +589,51 @@ int gpu_build_sah(const SahRec* recs_host, int n, int tri_base, float pad, const
 // Empty launches that load the GPU build's / the render kernels' code objects (scene-create warm-up).
 void gpu_bvh_warm(hipStream_t st);
 void device_warm(hipStream_t st);
+
+// SceneView::child_split as rtg_scene_create sets it (rtg_host.cpp): on unless RTG_CHILD_SPLIT=0 is in the
+// environment -- read per scene creation: a data switch for A/B runs and the tests, same device code.
+int child_split_default();
+
+#ifdef __HIPCC__
+// k_shade's compaction of a level's child rays and shadow queries (shade_ray, rtg_device.hip; called by
+// every thread of a BLOCK-thread block): ballot prefixes inside each wave, wave totals combined in LDS,
+// one 64-bit atomic per block on the level's queue counter (low word: rays, high word: shadow entries).
+// has0 / has1: the lane has a refracted / a reflected child; stot: the wave's shadow-list entries.
+// Returns the lane's queue positions idx0 / idx1 and the wave's first shadow-list position sb.
+// split (round 7): the block's range holds every wave's refracted children, then every wave's reflected
+// ones; otherwise each lane's two children are adjacent, in wave and lane order, as before.
+template <int BLOCK>
+__device__ inline void queue_slots(bool split, bool has0, bool has1, unsigned stot, unsigned long long* qcount, int& idx0,
+                                   int& idx1, unsigned& sb) {
+    __shared__ unsigned s_wc[BLOCK / 64], s_ws[BLOCK / 64], s_w1[BLOCK / 64];
+    __shared__ unsigned long long s_base;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long lt = __lanemask_lt();
+    const int nchild = (has0 ? 1 : 0) + (has1 ? 1 : 0);
+    const unsigned long long m1 = __ballot(split ? has0 : nchild >= 1), m2 = __ballot(split ? has1 : nchild >= 2);
+    const unsigned coff = __popcll(m1 & lt) + (split ? 0u : __popcll(m2 & lt));
+    if (lane == 0) { s_wc[w] = __popcll(m1) + (split ? 0u : __popcll(m2)); s_w1[w] = __popcll(m2); s_ws[w] = stot; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned c = 0, sh = 0;
+        for (int k = 0; k < BLOCK / 64; k++) {
+            const unsigned a = s_wc[k], b = s_ws[k];
+            s_wc[k] = c; s_ws[k] = sh;
+            c += a; sh += b;
+        }
+        if (split)          // the reflected children's ranges, after every wave's refracted ones
+            for (int k = 0; k < BLOCK / 64; k++) {
+                const unsigned a = s_w1[k];
+                s_w1[k] = c;
+                c += a;
+            }
+        s_base = (c | sh) ? atomicAdd(qcount, ((unsigned long long)sh << 32) | c) : 0ull;
+    }
+    __syncthreads();
+    idx0 = (int)((unsigned)s_base + s_wc[w] + coff);
+    idx1 = split ? (int)((unsigned)s_base + s_w1[w] + __popcll(m2 & lt)) : idx0 + (has0 ? 1 : 0);
+    sb = (unsigned)(s_base >> 32) + s_ws[w];
+}
+#endif
 
 }  // namespace rtg
