@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define RTG_ABI_VERSION 9
+#define RTG_ABI_VERSION 10
 
 typedef enum rtg_status {
     RTG_OK = 0,
@@ -501,6 +501,62 @@ int32_t rtg_scene_object_matrices(const rtg_scene* scene, int32_t top_object, fl
                                   float* inverse_transpose16);
 /* Smooth vertex normals after the precompute of renderScene (src/Scene.cpp:294-318): 3*num_vertices. */
 int32_t rtg_scene_vertex_normals(const rtg_scene* scene, float* normals);
+
+/* ---- ABI 10: resumable progressive frames -----------------------------------
+   An rtg_frame is a device-resident accumulator for one camera of one scene: the running float32
+   sum of every owned pixel's samples, in sample order, and optionally the running mean and M2
+   (Welford) of the samples' luminance.  Samples are added in index order, first_sample + done,
+   + 1, ...; sample k of a pixel is the same ray tree whichever call traces it (every random draw
+   is keyed by pixel and global sample index), and the sum continues ((s + c_k) + c_k+1) + ... as
+   one rtg_render does, so a frame over [0, num_samples) resolves, after any chunking, to exactly
+   what rtg_render returns for the same camera and options -- on either schedule.
+   The camera, seed, shard options (row_offset / row_stride / row_block / compact_rows), traversal,
+   schedule and batch options are fixed at creation.  num_devices > 1 or devices != NULL:
+   RTG_ERR_UNSUPPORTED.  The accumulator is the frame's own (12 B per owned pixel, + 8 B with
+   moments); the render workspace is the scene's, so calls on one scene must not be concurrent, but
+   frames and rtg_render calls may interleave.  rtg_scene_destroy fails with RTG_ERR_INVALID while
+   a scene has live frames. */
+typedef struct rtg_frame rtg_frame;
+typedef struct rtg_frame_opts {
+    int32_t first_sample;    /* first index of the camera's num_samples that this frame covers */
+    int32_t sample_count;    /* how many it covers; 0 = through the last one */
+    int32_t moments;         /* 1: keep a running mean and M2 of each pixel's sample luminance */
+    int32_t pad;
+} rtg_frame_opts;
+/* Error estimate over the owned pixels.  Y = (0.2126 R + 0.7152 G) + 0.0722 B of a sample, 0 when
+   negative or not finite; per pixel, variance = M2 / (n - 1) (0 for n < 2) and the standard error
+   of the mean sem = sqrt(variance / n), n = samples_done. */
+typedef struct rtg_frame_error {
+    double mean_luminance;   /* mean over the pixels of the per-pixel mean of Y */
+    double mean_sem;         /* mean over the pixels of sem */
+    double max_sem;
+    int32_t samples_done;
+    int32_t pixels;          /* owned pixels */
+} rtg_frame_error;
+/* opts / fopts may be NULL (defaults: seed 0, the whole camera, no moments). */
+int32_t rtg_frame_create(rtg_scene* scene, const rtg_camera_desc* cam, const rtg_render_opts* opts,
+                         const rtg_frame_opts* fopts, rtg_frame** out);
+/* Trace the next `count` samples of every owned pixel (work enqueued behind `stream`, a hipStream_t;
+   synchronous on return).  rtg_last_render_stats then describes this call alone. */
+int32_t rtg_frame_add_samples(rtg_frame* frame, int32_t count, void* stream);
+/* Samples accumulated so far (negative status for a NULL frame). */
+int32_t rtg_frame_samples_done(const rtg_frame* frame);
+/* sum / (float)samples_done for owned pixels, 0 for the others; layout as rtg_render (host) and
+   rtg_render_device. */
+int32_t rtg_frame_resolve(rtg_frame* frame, float* rgb_out);
+int32_t rtg_frame_resolve_device(rtg_frame* frame, float* rgb_out_device, void* stream);
+/* Per owned pixel, in owned-row order (rows_owned * nx floats each; either may be NULL): the mean
+   and the unbiased variance of the samples' luminance. */
+int32_t rtg_frame_moments(rtg_frame* frame, float* mean_out, float* variance_out);
+int32_t rtg_frame_error_stats(rtg_frame* frame, rtg_frame_error* out);
+/* Checkpoint: the raw sums (3 floats per owned pixel) and, for a frame with moments, mean and M2
+   (2 per owned pixel), to and from host memory.  A state restored into a frame of the same camera,
+   options and window -- of this scene or of another built from the same descriptor -- and continued
+   finishes bit-identical to an uninterrupted frame.  moments_out may be NULL; sums / moments may be
+   NULL when samples_done is 0. */
+int32_t rtg_frame_get_state(rtg_frame* frame, float* sums_out, float* moments_out);
+int32_t rtg_frame_set_state(rtg_frame* frame, int32_t samples_done, const float* sums, const float* moments);
+int32_t rtg_frame_destroy(rtg_frame* frame);
 
 #ifdef __cplusplus
 }

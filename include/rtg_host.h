@@ -54,6 +54,17 @@ int32_t rtgh_render_scene(const char* xml_path, int32_t device, uint64_t seed, c
    num_devices = 1 the one GPU is a one-rank RCCL job).  num_devices = 0: rtgh_render_scene. */
 int32_t rtgh_render_scene_multi(const char* xml_path, int32_t device, int32_t num_devices, uint64_t seed,
                                 const char* out_dir);
+/* Progressive (rtg_frame, include/rtg.h): every camera is rendered in rounds of `step` samples.  After
+   each round its image files are rewritten (the tone-mapped one too where the camera has a <Tonemap>)
+   and one line goes to stdout: "<name>: <done>/<total> spp, mean_sem <s>, mean_luminance <l>".
+   target_error > 0: a camera stops after the first round with mean_sem <= target_error *
+   max(mean_luminance, FLT_MIN) and at least two samples (one sample has no
+   variance).  Otherwise it runs to num_samples, and the final files are
+   byte-identical to rtgh_render_scene's.
+   (Declared `extern`: tests/test_host_native.py pins the twelve entry points above by their leading
+   return type; tests/test_frame_abi.py checks that this one is exported.) */
+extern int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                             int32_t step, double target_error);
 
 #ifdef __cplusplus
 }

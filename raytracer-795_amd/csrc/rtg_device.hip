@@ -2889,23 +2889,28 @@ constexpr int kAccPixWide = 256, kAccChunkWide = 16;
 // Colours are read from the level-0 NodePlanes colour plane; `resolve` (Whitted only) evaluates
 // non-final level-0 nodes against level 1 first.
 // DEEP (round 5): level 1 is resolved inline too (resolve_node2, against the resolved level 2).
-template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk>
-__global__ void __launch_bounds__(256) k_accumulate(const SceneView sv,
-                                                    const NodePlanes level0, const NodePlanes level1, bool resolve,
-                                                    float* __restrict__ acc, const PassDev ps, int nx, int mode,
-                                                    const NodePlanes level2) {
+// MOM (a frame with moments): the lane that sums a pixel's colours also continues the
+// running mean and M2 of the samples' luminance (Welford, one sample at a time in index order, float32;
+// mom holds mean and M2 per owned pixel in `acc` order, mom_k0 = the samples they already cover).  The
+// colours are in LDS already, so the moments cost no further HBM reads of per-sample records.
+template <bool DEEP, int PIX, int CHUNK, bool MOM>
+DEV void accumulate_body(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
+                         float* __restrict__ acc, const PassDev& ps, int nx, int mode, const NodePlanes& level2,
+                         float* __restrict__ mom, int mom_k0) {
     constexpr int kAccPix = PIX, kAccChunk = CHUNK, kAccStride = CHUNK + 1;
     __shared__ float sr[kAccPix * kAccStride], sg[kAccPix * kAccStride], sb[kAccPix * kAccStride];
     const int p0 = blockIdx.x * kAccPix;
     const int np = min(kAccPix, ps.npass - p0);
     const int t = threadIdx.x;
     f3 a = mk(0.0f, 0.0f, 0.0f);
+    float mean = 0.0f, m2 = 0.0f;
     size_t p = 0;
     if (t < np) {
         int x, k;
         tile_pixel(ps.p0 + p0 + t, nx, ps.rows_owned, ps.tile_h, ps.tile_s, x, k);
         p = (size_t)k * nx + x;                 // acc is in natural owned-row order
         if (mode == 0) a = mk(acc[3 * p], acc[3 * p + 1], acc[3 * p + 2]);
+        if (MOM && mom_k0 > 0) { mean = mom[2 * p]; m2 = mom[2 * p + 1]; }
     }
     for (int s0 = 0; s0 < ps.ns; s0 += kAccChunk) {
         const int cs = min(kAccChunk, ps.ns - s0);
@@ -2932,9 +2937,79 @@ __global__ void __launch_bounds__(256) k_accumulate(const SceneView sv,
                 s = 1;
             }
             for (; s < cs; s++) a = a + mk(sr[t * kAccStride + s], sg[t * kAccStride + s], sb[t * kAccStride + s]);
+            if (MOM)
+                for (int q = 0; q < cs; q++) {
+                    const float c[3] = {sr[t * kAccStride + q], sg[t * kAccStride + q], sb[t * kAccStride + q]};
+                    const float y = tm_lum(c);
+                    const float d = y - mean;
+                    mean = mean + d / (float)(mom_k0 + s0 + q + 1);
+                    m2 = m2 + d * (y - mean);
+                }
         }
     }
-    if (t < np) { acc[3 * p] = a.x; acc[3 * p + 1] = a.y; acc[3 * p + 2] = a.z; }
+    if (t < np) {
+        acc[3 * p] = a.x; acc[3 * p + 1] = a.y; acc[3 * p + 2] = a.z;
+        if (MOM) { mom[2 * p] = mean; mom[2 * p + 1] = m2; }
+    }
+}
+template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk>
+__global__ void __launch_bounds__(256) k_accumulate(const SceneView sv,
+                                                    const NodePlanes level0, const NodePlanes level1, bool resolve,
+                                                    float* __restrict__ acc, const PassDev ps, int nx, int mode,
+                                                    const NodePlanes level2) {
+    accumulate_body<DEEP, PIX, CHUNK, false>(sv, level0, level1, resolve, acc, ps, nx, mode, level2, nullptr, 0);
+}
+template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk>
+__global__ void __launch_bounds__(256) k_accumulate_mom(const SceneView sv,
+                                                        const NodePlanes level0, const NodePlanes level1, bool resolve,
+                                                        float* __restrict__ acc, const PassDev ps, int nx, int mode,
+                                                        const NodePlanes level2, float* __restrict__ mom, int mom_k0) {
+    accumulate_body<DEEP, PIX, CHUNK, true>(sv, level0, level1, resolve, acc, ps, nx, mode, level2, mom, mom_k0);
+}
+
+// rtg_frame_error_stats: one lane per owned pixel; the pixel's mean luminance and the standard error of
+// that mean, sqrt(variance / n) with variance = M2 / (n - 1) in float32 as rtg_frame_moments returns it,
+// reduced in double: shuffles inside each wave, the four wave results through LDS in wave order, one
+// partial triple per block; k_frame_error_final combines the partials in one block the same way.  The
+// shape depends only on the pixel count and nothing is added atomically, so the figures repeat.
+DEV void err_wave_reduce(double& a, double& b, double& c) {
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off, 64);
+        b += __shfl_down(b, off, 64);
+        c = fmax(c, __shfl_down(c, off, 64));
+    }
+}
+DEV void err_block_reduce(double a, double b, double c, double* __restrict__ out) {
+    __shared__ double sa[kErrBlock / 64], sb[kErrBlock / 64], sc[kErrBlock / 64];
+    err_wave_reduce(a, b, c);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { sa[w] = a; sb[w] = b; sc[w] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kErrBlock / 64; k++) { a += sa[k]; b += sb[k]; c = fmax(c, sc[k]); }
+        out[0] = a; out[1] = b; out[2] = c;
+    }
+}
+__global__ void __launch_bounds__(kErrBlock) k_frame_error(const float* __restrict__ mom, int npix, int n,
+                                                          double* __restrict__ part) {
+    const int i = blockIdx.x * kErrBlock + threadIdx.x;
+    double mean = 0.0, sem = 0.0;
+    if (i < npix) {
+        mean = (double)mom[2 * (size_t)i];
+        const float var = n >= 2 ? mom[2 * (size_t)i + 1] / (float)(n - 1) : 0.0f;
+        sem = sqrt((double)var / (double)n);
+    }
+    err_block_reduce(mean, sem, sem, part + 3 * (size_t)blockIdx.x);
+}
+__global__ void __launch_bounds__(kErrBlock) k_frame_error_final(const double* __restrict__ part, int nblocks,
+                                                                double* __restrict__ out) {
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (int k = threadIdx.x; k < nblocks; k += kErrBlock) {
+        a += part[3 * (size_t)k];
+        b += part[3 * (size_t)k + 1];
+        c = fmax(c, part[3 * (size_t)k + 2]);
+    }
+    err_block_reduce(a, b, c, out);
 }
 
 __global__ void __launch_bounds__(256) k_finalize(const float* __restrict__ acc, float* __restrict__ out, int nx,
@@ -3138,9 +3213,19 @@ void launch_resolve_planes(const SceneView& sv, const NodePlanes& self, const No
     hipLaunchKernelGGL(k_resolve, dim3(nblk(count, 256)), dim3(256), 0, st, sv, self, child, count);
 }
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st) {
+                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
     if (ps.npass <= 0) return;
-    if (!resolve || ps.ns <= kAccChunkWide)
+    const bool wide = !resolve || ps.ns <= kAccChunkWide;
+    if (mom) {      // a frame with moments: the same shapes, the luminance moments continued in the same launch
+        if (wide)
+            hipLaunchKernelGGL((k_accumulate_mom<false, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)),
+                               dim3(256), 0, st, sv, level0, level1, resolve, acc, ps, nx, mode, NodePlanes{}, mom, mom_k0);
+        else
+            hipLaunchKernelGGL(k_accumulate_mom<false>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, level0,
+                               level1, resolve, acc, ps, nx, mode, NodePlanes{}, mom, mom_k0);
+        return;
+    }
+    if (wide)
         hipLaunchKernelGGL((k_accumulate<false, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
                            0, st, sv, level0, level1, resolve, acc, ps, nx, mode, NodePlanes{});
     else
@@ -3149,26 +3234,34 @@ void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, con
 }
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
                        const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
-                       const NodeRec* level2, int n2) {
+                       const NodeRec* level2, int n2, float* mom, int mom_k0) {
     if (ps.npass <= 0) return;
     NodeRec* l0 = const_cast<NodeRec*>(level0);
     const NodePlanes p0 = node_planes(l0, n0);
     const NodePlanes p1 = (whitted && level1) ? node_planes(const_cast<NodeRec*>(level1), n1) : NodePlanes{};
     if (whitted && resolve && level1 && level2) {
         const NodePlanes p2 = node_planes(const_cast<NodeRec*>(level2), n2);
-        if (ps.ns <= kAccChunkWide)
+        if (mom) {
+            if (ps.ns <= kAccChunkWide)
+                hipLaunchKernelGGL((k_accumulate_mom<true, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)),
+                                   dim3(256), 0, st, sv, p0, p1, true, acc, ps, nx, mode, p2, mom, mom_k0);
+            else
+                hipLaunchKernelGGL(k_accumulate_mom<true>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1,
+                                   true, acc, ps, nx, mode, p2, mom, mom_k0);
+        } else if (ps.ns <= kAccChunkWide)
             hipLaunchKernelGGL((k_accumulate<true, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
                                0, st, sv, p0, p1, true, acc, ps, nx, mode, p2);
         else
             hipLaunchKernelGGL(k_accumulate<true>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1, true, acc,
                                ps, nx, mode, p2);
-    } else if (!(resolve && whitted) || ps.ns <= kAccChunkWide) {
-        hipLaunchKernelGGL((k_accumulate<false, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
-                           0, st, sv, p0, p1, resolve && whitted, acc, ps, nx, mode, NodePlanes{});
     } else {
-        hipLaunchKernelGGL(k_accumulate<false>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1,
-                           resolve && whitted, acc, ps, nx, mode, NodePlanes{});
+        launch_accumulate_planes(sv, p0, p1, resolve && whitted, acc, ps, nx, mode, st, mom, mom_k0);
     }
+}
+void launch_frame_error(const float* mom, int npix, int n, double* part, double* out, hipStream_t st) {
+    const int nb = nblk(std::max(npix, 1), kErrBlock);
+    hipLaunchKernelGGL(k_frame_error, dim3(nb), dim3(kErrBlock), 0, st, mom, npix, n, part);
+    hipLaunchKernelGGL(k_frame_error_final, dim3(1), dim3(kErrBlock), 0, st, part, nb, out);
 }
 void launch_finalize(const float* acc, float* out, int nx, int ny, int row_offset, int row_stride, int row_block,
                      int total, hipStream_t st) {

@@ -1382,7 +1382,7 @@ private:
 };
 static Reaper g_reaper;
 
-int32_t rtg_scene_destroy(rtg_scene* s) {
+static int32_t scene_destroy(rtg_scene* s) {     // rtg_scene_destroy (below, with the frames) once no frame is left
     if (!s) return RTG_OK;
     g_reaper.drain();
     if (s->device >= 0) (void)hipSetDevice(s->device);
@@ -2486,7 +2486,7 @@ static CameraDev make_camera(const rtg_camera_desc* c) {
 }
 
 static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, float* out_dev,
-                       hipStream_t st) {
+                       hipStream_t st, const RenderTarget* target = nullptr) {
     if (cam->nx < 1 || cam->ny < 1 || cam->num_samples < 1) return fail(RTG_ERR_INVALID, "bad camera");
     rtg_render_opts o{};
     if (opts) o = *opts;
@@ -2500,7 +2500,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     long long npix_ll = (long long)rows_owned * cam->nx;
     if (npix_ll > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
     int npix = (int)npix_ll;
-    int total = cam->num_samples;
+    RenderTarget tg = target ? *target : RenderTarget{nullptr, nullptr, 0, cam->num_samples, 0}; const int total = tg.ns;   // samples per pixel of this call
     if (cam->integrator != RTG_INTEGRATOR_REFERENCE && cam->integrator != RTG_INTEGRATOR_PATH)
         return fail(RTG_ERR_INVALID, "unknown integrator");
     const bool pt = cam->integrator == RTG_INTEGRATOR_PATH;
@@ -2548,7 +2548,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     int exhaustive = o.traversal == 1;
 
     int rc;
-    if ((rc = s->d_acc.grow(sizeof(float) * 3 * std::max<size_t>(npix, 1)))) return rc;
+    if (!tg.acc) { if ((rc = s->d_acc.grow(sizeof(float) * 3 * std::max<size_t>(npix, 1)))) return rc; tg.acc = s->d_acc.as<float>(); }
     // d_cnt[0]: NaN shadow queries (all passes)
     if ((rc = s->d_counters.grow(sizeof(unsigned) * 64))) return rc;
     if ((rc = s->d_stats.grow(sizeof(Counters)))) return rc;
@@ -2591,7 +2591,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     for (int p0 = 0; p0 < npix; p0 += np_pass)
         for (int s0 = 0; s0 < total; s0 += ns_chunk) {
             PassDev ps;
-            ps.s0 = s0; ps.ns = std::min(ns_chunk, total - s0);
+            ps.s0 = tg.s0 + s0; ps.ns = std::min(ns_chunk, total - s0);
             ps.p0 = p0; ps.npass = std::min(np_pass, npix - p0);
             ps.row_offset = off; ps.row_stride = stride; ps.rows_owned = rows_owned; ps.row_block = block;
             ps.tile_h = tile_h;
@@ -2736,15 +2736,15 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             (rc2 = timed_launch(ln, [&] { launch_resolve(sv, N(2), N(3), ln.counts[2], ln.counts[3], ln.st); },
                                 stt.resolve_ms, stt.resolve_launches)))
             return rc2;
-        const int mode = (total == 1) ? 2 : (ps.s0 == 0 ? 1 : 0);
+        const int before = tg.have + (ps.s0 - tg.s0), mode = (cam->num_samples == 1) ? 2 : (before == 0 ? 1 : 0);   // before: samples already summed
         const NodeRec* level1 = level >= 1 ? N(1) : nullptr;
         const NodeRec* level2 = level >= 2 ? N(2) : nullptr;
         if ((rc2 = timed_launch(ln, [&] {
                  // (the path tracer: the pass's sample radiance, PtRad)
-                 launch_accumulate(sv, pt ? ln.prad.as<NodeRec>() : N(0), level1, !pt && level >= 1, s->d_acc.as<float>(), ps,
+                 launch_accumulate(sv, pt ? ln.prad.as<NodeRec>() : N(0), level1, !pt && level >= 1, tg.acc, ps,
                                    cam->nx, mode, ln.st, !pt,
                                    ln.counts[0], level >= 1 ? ln.counts[1] : 0, pt ? nullptr : level2,
-                                   level >= 2 ? ln.counts[2] : 0);
+                                   level >= 2 ? ln.counts[2] : 0, tg.mom, before);
              }, stt.accumulate_ms, stt.accumulate_launches)))
             return rc2;
         stt.passes++;
@@ -2828,7 +2828,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             HIP_TRY(hipStreamWaitEvent(ln.st, e0, 0));
         }
         PassDev F;
-        F.s0 = 0; F.ns = total; F.p0 = 0; F.npass = npix;
+        F.s0 = tg.s0; F.ns = total; F.p0 = 0; F.npass = npix;
         F.row_offset = off; F.row_stride = stride; F.rows_owned = rows_owned; F.row_block = block;
         F.tile_h = tile_h;
         F.tile_s = tile_s;
@@ -2982,7 +2982,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
                     ln.busy = false;
                 }
             }
-            const int mode = total == 1 ? 2 : 1;
+            const int mode = cam->num_samples == 1 ? 2 : (tg.have == 0 ? 1 : 0);
             if (pt) {
                 // the segment's paths have ended: sum every pixel's samples in order, on lane 0 once
                 // every lane's last gather is done; the next segment's gathers wait for that sum
@@ -2992,8 +2992,8 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
                     HIP_TRY(hipStreamWaitEvent(l0.st, s->lanes[k].ev_join, 0));
                 }
                 if ((rc = timed_launch(l0, [&] {
-                         launch_accumulate(sv, s->d_rad.as<NodeRec>(), nullptr, false, s->d_acc.as<float>(), F, cam->nx,
-                                           mode, l0.st, /*whitted=*/false, (int)seg_slots, 0);
+                         launch_accumulate(sv, s->d_rad.as<NodeRec>(), nullptr, false, tg.acc, F, cam->nx,
+                                           mode, l0.st, /*whitted=*/false, (int)seg_slots, 0, nullptr, 0, tg.mom, tg.have);
                      }, stt.accumulate_ms, stt.accumulate_launches)))
                     return rc;
                 HIP_TRY(hipEventRecord(l0.ev_join, l0.st));
@@ -3021,8 +3021,8 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
                             P.p0 = ln.step_gb[j] / total;
                             P.npass = ln.step_g[j] / total;
                             if ((rc = timed_launch(ln, [&] {
-                                     launch_accumulate_planes(sv, l0, child, true, s->d_acc.as<float>(), P, cam->nx, mode,
-                                                              ln.st);
+                                     launch_accumulate_planes(sv, l0, child, true, tg.acc, P, cam->nx, mode,
+                                                              ln.st, tg.mom, tg.have);
                                  }, stt.accumulate_ms, stt.accumulate_launches)))
                                 return rc;
                         }
@@ -3087,10 +3087,11 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
         HIP_TRY(hipEventRecord(ejoin, s->lanes[k].st));
         HIP_TRY(hipStreamWaitEvent(st, ejoin, 0));
     }
-    if (o.compact_rows)
-        launch_finalize(s->d_acc.as<float>(), out_dev, cam->nx, rows_owned, 0, 1, 1, total, st);
-    else
-        launch_finalize(s->d_acc.as<float>(), out_dev, cam->nx, cam->ny, off, stride, block, total, st);
+    // (no out_dev: a frame, which resolves on request -- rtg_frame_resolve*)
+    if (out_dev && o.compact_rows)
+        launch_finalize(tg.acc, out_dev, cam->nx, rows_owned, 0, 1, 1, total, st);
+    else if (out_dev)
+        launch_finalize(tg.acc, out_dev, cam->nx, cam->ny, off, stride, block, total, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e1, st));
     HIP_TRY(hipEventSynchronize(e1));
@@ -3242,6 +3243,241 @@ int32_t rtg_render(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_op
         }
         (void)hipFree(d_out);
         return rc;
+    });
+}
+
+// ---------------------------------------------------------------- progressive frames (ABI 10)
+}  // extern "C"
+
+// A progressive frame (include/rtg.h): one camera's accumulator, outliving the calls.
+struct rtg_frame {
+    rtg_scene* scene = nullptr;
+    rtg_camera_desc cam{};
+    rtg_render_opts opts{};
+    int first = 0, count = 0;                // the window of the camera's samples
+    int done = 0;                            // samples accumulated, in index order from `first`
+    bool moments = false;
+    bool broken = false;                     // an add failed half-way: the sums are undefined until set_state
+    int rows_owned = 0, npix = 0;
+    DBuf acc, mom;                           // 3 / 2 floats per owned pixel, owned-row order
+    DBuf err;                                // error_stats: per-block partials + the 3 results (doubles)
+};
+
+// The scene of every live frame (one entry per frame): a scene stays while frames render through it.
+static std::mutex g_frames_mu;
+static std::vector<const rtg_scene*> g_frame_scenes;
+
+extern "C" {
+
+int32_t rtg_scene_destroy(rtg_scene* s) {
+    if (s) {
+        std::lock_guard<std::mutex> lk(g_frames_mu);
+        if (std::count(g_frame_scenes.begin(), g_frame_scenes.end(), s) > 0)
+            return fail(RTG_ERR_INVALID, "scene has live frames: destroy them first");
+    }
+    return scene_destroy(s);
+}
+
+int32_t rtg_frame_create(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts,
+                         const rtg_frame_opts* fopts, rtg_frame** out) {
+    return guarded([&]() -> int32_t {
+        if (out) *out = nullptr;
+        if (!s || !cam || !out) return fail(RTG_ERR_INVALID, "null argument");
+        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+        if (cam->nx < 1 || cam->ny < 1 || cam->num_samples < 1) return fail(RTG_ERR_INVALID, "bad camera");
+        if (cam->integrator != RTG_INTEGRATOR_REFERENCE && cam->integrator != RTG_INTEGRATOR_PATH)
+            return fail(RTG_ERR_INVALID, "unknown integrator");
+        rtg_render_opts o{};
+        if (opts) o = *opts;
+        if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_UNSUPPORTED, "frames render on the scene's device only");
+        const int stride = o.row_stride > 1 ? o.row_stride : 1, block = o.row_block > 1 ? o.row_block : 1;
+        if (o.row_offset < 0 || o.row_offset >= stride) return fail(RTG_ERR_INVALID, "row_offset out of range");
+        if (o.schedule < RTG_SCHEDULE_AUTO || o.schedule > RTG_SCHEDULE_STREAM) return fail(RTG_ERR_INVALID, "schedule");
+        if (o.tile_band < 0 || o.segment_pixels < 0 || o.segment_nodes < 0)
+            return fail(RTG_ERR_INVALID, "tile_band / segment_pixels / segment_nodes");
+        rtg_frame_opts fo{};
+        if (fopts) fo = *fopts;
+        if (fo.first_sample < 0 || fo.first_sample >= cam->num_samples || fo.sample_count < 0 ||
+            fo.sample_count > cam->num_samples - fo.first_sample)
+            return fail(RTG_ERR_INVALID, "frame window outside the camera's samples");
+        const int rows = rtg_shard_rows(cam->ny, o.row_offset, stride, block);
+        if ((long long)rows * cam->nx > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
+        HIP_TRY(hipSetDevice(s->device));
+        rtg_frame* f = new (std::nothrow) rtg_frame();
+        if (!f) return fail(RTG_ERR_OOM, "host allocation");
+        f->scene = s;
+        f->cam = *cam;
+        f->opts = o;
+        f->first = fo.first_sample;
+        f->count = fo.sample_count > 0 ? fo.sample_count : cam->num_samples - fo.first_sample;
+        f->moments = fo.moments != 0;
+        f->rows_owned = rows;
+        f->npix = rows * cam->nx;
+        int rc = f->acc.grow(sizeof(float) * 3 * std::max<size_t>(f->npix, 1));
+        if (!rc && f->moments) rc = f->mom.grow(sizeof(float) * 2 * std::max<size_t>(f->npix, 1));
+        if (rc) { f->acc.release(); f->mom.release(); delete f; return rc; }
+        {
+            std::lock_guard<std::mutex> lk(g_frames_mu);
+            g_frame_scenes.push_back(s);
+        }
+        *out = f;
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_destroy(rtg_frame* f) {
+    if (!f) return RTG_OK;
+    if (f->scene->device >= 0) (void)hipSetDevice(f->scene->device);
+    f->acc.release(); f->mom.release(); f->err.release();
+    {
+        std::lock_guard<std::mutex> lk(g_frames_mu);
+        const auto it = std::find(g_frame_scenes.begin(), g_frame_scenes.end(), f->scene);
+        if (it != g_frame_scenes.end()) g_frame_scenes.erase(it);
+    }
+    delete f;
+    return RTG_OK;
+}
+
+int32_t rtg_frame_samples_done(const rtg_frame* f) {
+    if (!f) return fail(RTG_ERR_INVALID, "null argument");
+    return f->done;
+}
+
+int32_t rtg_frame_add_samples(rtg_frame* f, int32_t count, void* stream) {
+    return guarded([&]() -> int32_t {
+        if (!f) return fail(RTG_ERR_INVALID, "null argument");
+        if (f->broken) return fail(RTG_ERR_INVALID, "frame state lost by a failed call: restore it with rtg_frame_set_state");
+        if (count <= 0) return fail(RTG_ERR_INVALID, "sample count must be positive");
+        if (count > f->count - f->done) return fail(RTG_ERR_INVALID, "more samples than the frame's window has left");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        const RenderTarget tg{f->acc.as<float>(), f->moments ? f->mom.as<float>() : nullptr, f->first + f->done, count,
+                              f->done};
+        const int rc = render_impl(f->scene, &f->cam, &f->opts, nullptr, (hipStream_t)stream, &tg);
+        if (rc) {
+            f->broken = true;
+            return rc;
+        }
+        f->done += count;
+        return RTG_OK;
+    });
+}
+
+static int frame_ready(const rtg_frame* f, bool need_moments) {
+    if (!f) return fail(RTG_ERR_INVALID, "null argument");
+    if (f->broken) return fail(RTG_ERR_INVALID, "frame state lost by a failed call: restore it with rtg_frame_set_state");
+    if (need_moments && !f->moments) return fail(RTG_ERR_INVALID, "frame was created without moments");
+    if (f->done < 1) return fail(RTG_ERR_INVALID, "frame has no samples yet");
+    return RTG_OK;
+}
+
+int32_t rtg_frame_resolve_device(rtg_frame* f, float* rgb_out_device, void* stream) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_ready(f, false);
+        if (rc) return rc;
+        if (!rgb_out_device) return fail(RTG_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        const hipStream_t st = (hipStream_t)stream;
+        const rtg_render_opts& o = f->opts;
+        // k_finalize divides when its count exceeds 1 (x / 1.0f is x)
+        if (o.compact_rows)
+            launch_finalize(f->acc.as<float>(), rgb_out_device, f->cam.nx, f->rows_owned, 0, 1, 1, f->done, st);
+        else
+            launch_finalize(f->acc.as<float>(), rgb_out_device, f->cam.nx, f->cam.ny, o.row_offset,
+                            o.row_stride > 1 ? o.row_stride : 1, o.row_block > 1 ? o.row_block : 1, f->done, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_resolve(rtg_frame* f, float* rgb_out) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_ready(f, false);
+        if (rc) return rc;
+        if (!rgb_out) return fail(RTG_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        const int out_rows = f->opts.compact_rows ? f->rows_owned : f->cam.ny;
+        const size_t bytes = sizeof(float) * 3 * (size_t)f->cam.nx * std::max(out_rows, 1);
+        float* d_out = nullptr;
+        HIP_TRY(hipMalloc(&d_out, bytes));
+        rc = rtg_frame_resolve_device(f, d_out, nullptr);
+        if (rc == RTG_OK) {
+            const hipError_t e = hipMemcpy(rgb_out, d_out, bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(RTG_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(d_out);
+        return rc;
+    });
+}
+
+int32_t rtg_frame_moments(rtg_frame* f, float* mean_out, float* variance_out) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_ready(f, true);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(f->scene->device));
+        std::vector<float> m((size_t)2 * f->npix);
+        if (f->npix) HIP_TRY(hipMemcpy(m.data(), f->mom.p, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
+        const int n = f->done;
+        for (int i = 0; i < f->npix; i++) {
+            if (mean_out) mean_out[i] = m[2 * (size_t)i];
+            if (variance_out) variance_out[i] = n >= 2 ? m[2 * (size_t)i + 1] / (float)(n - 1) : 0.0f;
+        }
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_error_stats(rtg_frame* f, rtg_frame_error* out) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_ready(f, true);
+        if (rc) return rc;
+        if (!out) return fail(RTG_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        const size_t nb = ((size_t)std::max(f->npix, 1) + kErrBlock - 1) / kErrBlock;
+        if ((rc = f->err.grow(sizeof(double) * 3 * (nb + 1)))) return rc;
+        double* part = f->err.as<double>();
+        double* res = part + 3 * nb;
+        launch_frame_error(f->mom.as<float>(), f->npix, f->done, part, res, nullptr);
+        HIP_TRY(hipGetLastError());
+        double h[3] = {0.0, 0.0, 0.0};
+        HIP_TRY(hipMemcpy(h, res, sizeof h, hipMemcpyDeviceToHost));
+        const double np = (double)std::max(f->npix, 1);
+        out->mean_luminance = h[0] / np;
+        out->mean_sem = h[1] / np;
+        out->max_sem = h[2];
+        out->samples_done = f->done;
+        out->pixels = f->npix;
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_get_state(rtg_frame* f, float* sums_out, float* moments_out) {
+    return guarded([&]() -> int32_t {
+        if (!f) return fail(RTG_ERR_INVALID, "null argument");
+        if (f->broken) return fail(RTG_ERR_INVALID, "frame state lost by a failed call: restore it with rtg_frame_set_state");
+        if (f->done == 0 || f->npix == 0) return RTG_OK;     // nothing defined yet
+        if (!sums_out) return fail(RTG_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        HIP_TRY(hipMemcpy(sums_out, f->acc.p, sizeof(float) * 3 * (size_t)f->npix, hipMemcpyDeviceToHost));
+        if (f->moments && moments_out)
+            HIP_TRY(hipMemcpy(moments_out, f->mom.p, sizeof(float) * 2 * (size_t)f->npix, hipMemcpyDeviceToHost));
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_set_state(rtg_frame* f, int32_t samples_done, const float* sums, const float* moments) {
+    return guarded([&]() -> int32_t {
+        if (!f) return fail(RTG_ERR_INVALID, "null argument");
+        if (samples_done < 0 || samples_done > f->count) return fail(RTG_ERR_INVALID, "samples_done outside the frame's window");
+        if (samples_done > 0 && (!sums || (f->moments && !moments))) return fail(RTG_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        if (samples_done > 0 && f->npix > 0) {
+            HIP_TRY(hipMemcpy(f->acc.p, sums, sizeof(float) * 3 * (size_t)f->npix, hipMemcpyHostToDevice));
+            if (f->moments)
+                HIP_TRY(hipMemcpy(f->mom.p, moments, sizeof(float) * 2 * (size_t)f->npix, hipMemcpyHostToDevice));
+        }
+        f->done = samples_done;
+        f->broken = false;
+        return RTG_OK;
     });
 }
 

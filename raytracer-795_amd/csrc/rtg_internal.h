@@ -448,8 +448,21 @@ void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const Pa
 // [0, count) against the next step's; the primaries of a pixel range at an offset of a step's planes)
 void launch_resolve_planes(const SceneView& sv, const NodePlanes& self, const NodePlanes& child, int count,
                            hipStream_t st);
+// Where a render's samples go.  rtg_render*: the scene's accumulator, the camera's whole sample range,
+// nothing accumulated before, no moments (target == nullptr).  A frame (rtg_frame_add_samples): its own
+// accumulator, samples [s0, s0 + ns) of the camera's, behind `have` samples the accumulator already holds.
+struct RenderTarget {
+    float* acc;       // running float32 sums, 3 per owned pixel in owned-row order
+    float* mom;       // mean and M2 of the samples' luminance, 2 per owned pixel, or null
+    int s0, ns;       // the window of the camera's samples this call traces
+    int have;         // samples already in acc / mom
+};
+
+// mom (a frame's moments, or null): mean and M2 of each pixel's sample luminance (2 floats per owned
+// pixel, in `acc` order), continued over this launch's samples; mom_k0 = samples they already hold
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st);
+                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
+                              int mom_k0 = 0);
 void launch_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, const unsigned* scount, NodeRec* nodes,
                    int n, int exhaustive, Counters* ctr, unsigned* nan_queries, hipStream_t st, bool whitted = true, int uni_from = INT_MAX);  // uni_from: first camera-sample node (wave-uniform walk)
 // the path tracer's queries: one launch per light, in light order (PtRad)
@@ -470,7 +483,12 @@ void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_n
 // level2 (optional): level 1 is resolved inline against it (the bottom-up pass left level 1 unresolved)
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
                        const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
-                       const NodeRec* level2 = nullptr, int n2 = 0);
+                       const NodeRec* level2 = nullptr, int n2 = 0, float* mom = nullptr, int mom_k0 = 0);
+// A frame's error figures (rtg_frame_error_stats): per-block double partials of the per-pixel mean and
+// standard error (3 doubles per block of 256 pixels in `part`: sum of means, sum of sems, max sem),
+// combined by one block into out[0..2] (sums, max) -- no atomics, so the figures repeat
+constexpr int kErrBlock = 256;
+void launch_frame_error(const float* mom, int npix, int n, double* part, double* out, hipStream_t st);
 void launch_finalize(const float* acc, float* out, int nx, int ny, int row_offset, int row_stride, int row_block, int total,
                      hipStream_t st);
 void launch_hit_details(const SceneView& sv, const RayQ rays, const HitRec* hits, struct ::rtg_hit* out,
@@ -633,6 +651,13 @@ __device__ inline void queue_slots(bool split, bool has0, bool has1, unsigned st
     idx0 = (int)((unsigned)s_base + s_wc[w] + coff);
     idx1 = split ? (int)((unsigned)s_base + s_w1[w] + __popcll(m2 & lt)) : idx0 + (has0 ? 1 : 0);
     sb = (unsigned)(s_base >> 32) + s_ws[w];
+}
+
+// Luminance of a colour as the tone mapper and a frame's moments (§14) define it:
+// 0 when negative or not finite.
+__device__ __forceinline__ float tm_lum(const float* c) {
+    const float y = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2];
+    return (__builtin_isfinite(y) && y > 0.0f) ? y : 0.0f;
 }
 #endif
 

@@ -24,11 +24,7 @@ namespace {
 
 constexpr int kTmBlock = 256;
 
-__device__ __forceinline__ float tm_lum(const float* c) {
-    const float y = (0.2126f * c[0] + 0.7152f * c[1]) + 0.0722f * c[2];
-    return (__builtin_isfinite(y) && y > 0.0f) ? y : 0.0f;
-}
-
+// (tm_lum: rtg_internal.h, shared with the frames' luminance moments)
 // Y per pixel and one double partial of log(1e-5 + Y) per block (fixed tree order)
 __global__ void __launch_bounds__(kTmBlock) k_tm_lum(const float* __restrict__ hdr, int n, float* __restrict__ Y,
                                                     double* __restrict__ part) {

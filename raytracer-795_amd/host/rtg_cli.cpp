@@ -7,6 +7,14 @@
 // --devices G renders every camera on G GPUs (device N and the next G-1): one host thread per
 // GPU, row-block pixel shards, RCCL gather of the rows onto device N -- the reference's
 // renderScene fork over 8 std::threads (src/Scene.cpp:294-363, threads at 340-356) moved to GPUs.
+//
+//   rtg_cli scene.xml --progressive K [--target-error E] [--device N] [--seed S] [--out-dir DIR]
+//
+// --progressive K renders every camera in rounds of K samples on a resumable frame (rtg_frame): after each
+// round the image files are rewritten and a line with the samples done, the mean standard error of the
+// pixels' luminance and their mean luminance is printed.  --target-error E stops a camera after the first
+// round with mean_sem <= E x mean_luminance; without it (or with E = 0) the render runs to NumSamples and
+// the files equal those of a run without --progressive, byte for byte.  One GPU only.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,21 +24,35 @@
 int main(int argc, char** argv) {
     const char* xml = nullptr;
     const char* out_dir = nullptr;
-    int device = 0, devices = 0;
+    int device = 0, devices = 0, progressive = 0;
+    bool have_progressive = false, have_target = false;
+    double target_error = 0.0;
     unsigned long long seed = 0x5EED2026ull;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = strtoull(argv[++i], nullptr, 0);
         else if (!strcmp(argv[i], "--out-dir") && i + 1 < argc) out_dir = argv[++i];
+        else if (!strcmp(argv[i], "--progressive") && i + 1 < argc) { progressive = atoi(argv[++i]); have_progressive = true; }
+        else if (!strcmp(argv[i], "--target-error") && i + 1 < argc) { target_error = atof(argv[++i]); have_target = true; }
         else if (argv[i][0] == '-') { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         else xml = argv[i];
     }
     if (!xml) {
-        fprintf(stderr, "usage: %s scene.xml [--device N] [--devices G] [--seed S] [--out-dir DIR]\n", argv[0]);
+        fprintf(stderr, "usage: %s scene.xml [--device N] [--devices G] [--seed S] [--out-dir DIR] "
+                        "[--progressive K [--target-error E]]\n", argv[0]);
         return 2;
     }
-    const int rc = rtgh_render_scene_multi(xml, device, devices, seed, out_dir);
+    if (have_progressive && devices > 0) {
+        fprintf(stderr, "rtg_cli: --progressive renders on one GPU: it cannot be combined with --devices\n");
+        return 2;
+    }
+    if ((have_progressive && progressive < 1) || (have_target && (!have_progressive || !(target_error >= 0.0)))) {
+        fprintf(stderr, "rtg_cli: --progressive needs K >= 1, --target-error needs --progressive and E >= 0\n");
+        return 2;
+    }
+    const int rc = have_progressive ? rtgh_render_scene_progressive(xml, device, seed, out_dir, progressive, target_error)
+                                    : rtgh_render_scene_multi(xml, device, devices, seed, out_dir);
     if (rc != RTG_OK) {
         fprintf(stderr, "rtg_cli: %s\n", rtgh_last_error());
         return 1;

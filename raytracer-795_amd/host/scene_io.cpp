@@ -1092,6 +1092,36 @@ int32_t rtgh_render_scene(const char* xml_path, int32_t device, uint64_t seed, c
     return rtgh_render_scene_multi(xml_path, device, 0, seed, out_dir);
 }
 
+// Where a camera's image goes: its <ImageName>, or that file name under out_dir.
+static std::string output_name(const CamData& c, const char* out_dir) {
+    std::string name = c.image_name;
+    if (out_dir && *out_dir) {
+        const size_t s = name.rfind('/');
+        name = std::string(out_dir) + "/" + (s == std::string::npos ? name : name.substr(s + 1));
+    }
+    return name;
+}
+
+// A camera's files.  hw5 <Tonemap>: the tone-mapped image goes to the name with a .png extension (a .png
+// ImageName is written tone-mapped instead of clamped), the HDR one to ImageName.
+static int save_camera_images(const CamData& c, const std::string& name, const std::vector<float>& rgb, int32_t device) {
+    int rc = RTG_OK;
+    const bool png = is_png(name.c_str());
+    if (!c.has_tonemap || !png) {
+        rc = rtgh_save_image(name.c_str(), rgb.data(), c.d.nx, c.d.ny);
+        if (rc) return rc;
+    }
+    if (c.has_tonemap) {
+        std::vector<float> ldr(rgb.size());
+        rc = rtg_tonemap(device, rgb.data(), c.d.nx, c.d.ny, &c.tm, ldr.data());
+        if (rc) { g_err = rtg_last_error(); return rc; }
+        const size_t dot = name.rfind('.'), sl = name.rfind('/');
+        const std::string tname = (dot == std::string::npos || (sl != std::string::npos && dot < sl) ? name : name.substr(0, dot)) + ".png";
+        rc = rtgh_save_image(tname.c_str(), ldr.data(), c.d.nx, c.d.ny);
+    }
+    return rc;
+}
+
 int32_t rtgh_render_scene_multi(const char* xml_path, int32_t device, int32_t num_devices, uint64_t seed,
                                 const char* out_dir) {
     return guarded([&]() -> int32_t {
@@ -1119,31 +1149,67 @@ int32_t rtgh_render_scene_multi(const char* xml_path, int32_t device, int32_t nu
             o.devices = num_devices > 0 ? devs.data() : nullptr;
             rc = rtg_render(gpu, &c.d, &o, rgb.data());
             if (rc) { g_err = rtg_last_error(); break; }
-            std::string name = c.image_name;
-            if (out_dir && *out_dir) {
-                const size_t s = name.rfind('/');
-                name = std::string(out_dir) + "/" + (s == std::string::npos ? name : name.substr(s + 1));
-            }
-            // hw5 <Tonemap>: the tone-mapped image goes to the name with a .png extension (a .png
-            // ImageName is written tone-mapped instead of clamped), the HDR one to ImageName
-            const bool png = is_png(name.c_str());
-            if (!c.has_tonemap || !png) {
-                rc = rtgh_save_image(name.c_str(), rgb.data(), c.d.nx, c.d.ny);
-                if (rc) break;
-            }
-            if (c.has_tonemap) {
-                std::vector<float> ldr(rgb.size());
-                rc = rtg_tonemap(device, rgb.data(), c.d.nx, c.d.ny, &c.tm, ldr.data());
-                if (rc) { g_err = rtg_last_error(); break; }
-                const size_t dot = name.rfind('.'), sl = name.rfind('/');
-                const std::string tname = (dot == std::string::npos || (sl != std::string::npos && dot < sl) ? name : name.substr(0, dot)) + ".png";
-                rc = rtgh_save_image(tname.c_str(), ldr.data(), c.d.nx, c.d.ny);
-                if (rc) break;
-            }
+            const std::string name = output_name(c, out_dir);
+            rc = save_camera_images(c, name, rgb, device);
+            if (rc) break;
             rtg_render_stats st{};
             rtg_last_render_stats(gpu, &st);
             printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s\n", name.c_str(), st.render_ms, st.total_rays / (st.render_ms * 1e3),
                    st.devices, st.devices == 1 ? "" : "s");
+        }
+        rtg_scene_destroy(gpu);
+        rtgh_free(sc);
+        return rc;
+    });
+}
+
+// The same camera loop on progressive frames (rtg_frame): rounds of `step` samples, the files rewritten
+// and an error line printed after each, a camera stopped early once its mean standard error is small
+// enough against its mean luminance.
+int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                      int32_t step, double target_error) {
+    return guarded([&]() -> int32_t {
+        if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
+        if (!(target_error >= 0.0)) return fail(RTG_ERR_INVALID, "target error must not be negative");
+        const double kFltMin = 1.17549435082228750797e-38;     // FLT_MIN
+        rtgh_scene* sc = nullptr;
+        int rc = rtgh_parse_xml(xml_path, &sc);
+        if (rc) return rc;
+        rtg_scene* gpu = nullptr;
+        rtg_build_opts bo{};
+        bo.bvh_builder = RTG_BVH_AUTO;
+        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
+        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
+        printf("BVH construction complete.\n");
+        for (const CamData& c : sc->cameras) {
+            std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
+            rtg_render_opts o{};
+            o.seed = seed;
+            rtg_frame_opts fo{};
+            fo.moments = 1;
+            rtg_frame* fr = nullptr;
+            rc = rtg_frame_create(gpu, &c.d, &o, &fo, &fr);
+            if (rc) { g_err = rtg_last_error(); break; }
+            const std::string name = output_name(c, out_dir);
+            const int total = c.d.num_samples;
+            for (int done = 0; done < total && rc == RTG_OK;) {
+                const int n = step < total - done ? step : total - done;
+                rtg_frame_error er{};
+                if ((rc = rtg_frame_add_samples(fr, n, nullptr)) || (rc = rtg_frame_resolve(fr, rgb.data())) ||
+                    (rc = rtg_frame_error_stats(fr, &er))) {
+                    g_err = rtg_last_error();
+                    break;
+                }
+                done += n;
+                if ((rc = save_camera_images(c, name, rgb, device))) break;
+                printf("%s: %d/%d spp, mean_sem %.6g, mean_luminance %.6g\n", name.c_str(), done, total, er.mean_sem,
+                       er.mean_luminance);
+                fflush(stdout);
+                // (one sample has no variance yet: its standard error reads 0, which is no reason to stop)
+                if (target_error > 0.0 && done >= 2 && er.mean_sem <= target_error * (er.mean_luminance > kFltMin ? er.mean_luminance : kFltMin)) break;
+            }
+            rtg_frame_destroy(fr);
+            if (rc) break;
         }
         rtg_scene_destroy(gpu);
         rtgh_free(sc);

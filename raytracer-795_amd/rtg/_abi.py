@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-RTG_ABI_VERSION = 9
+RTG_ABI_VERSION = 10
 
 RTG_OK = 0
 RTG_DEVICE_HOST_ONLY = -1
@@ -172,6 +172,16 @@ class TonemapDesc(C.Structure):
 TMO_PHOTOGRAPHIC = 0
 
 
+class FrameOpts(C.Structure):
+    _fields_ = [("first_sample", C.c_int32), ("sample_count", C.c_int32), ("moments", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class FrameError(C.Structure):
+    _fields_ = [("mean_luminance", C.c_double), ("mean_sem", C.c_double), ("max_sem", C.c_double),
+                ("samples_done", C.c_int32), ("pixels", C.c_int32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("full", C.c_int32), ("object", C.c_int32), ("prim", C.c_int32), ("material", C.c_int32),
                 ("t", C.c_float), ("point", F3), ("normal", F3)]
@@ -207,6 +217,18 @@ EXPORTS = {
     "rtg_comm_destroy": (C.c_int32, [C.c_void_p]),
     "rtg_render_ranked": (C.c_int32, [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderOpts), C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    # ABI 10: progressive frames
+    "rtg_frame_create": (C.c_int32, [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderOpts), C.POINTER(FrameOpts),
+                                     C.POINTER(C.c_void_p)]),
+    "rtg_frame_add_samples": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtg_frame_samples_done": (C.c_int32, [C.c_void_p]),
+    "rtg_frame_resolve": (C.c_int32, [C.c_void_p, PF]),
+    "rtg_frame_resolve_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtg_frame_moments": (C.c_int32, [C.c_void_p, PF, PF]),
+    "rtg_frame_error_stats": (C.c_int32, [C.c_void_p, C.POINTER(FrameError)]),
+    "rtg_frame_get_state": (C.c_int32, [C.c_void_p, PF, PF]),
+    "rtg_frame_set_state": (C.c_int32, [C.c_void_p, C.c_int32, PF, PF]),
+    "rtg_frame_destroy": (C.c_int32, [C.c_void_p]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -241,9 +263,9 @@ def load_library(path: str | None = None):
         fn.restype = res
         fn.argtypes = args
     v = lib.rtg_abi_version()
-    # dev A/B variants (RTG_LIBRARY) may be one ABI older: ABI 9 only appended rtg_render_stats fields,
-    # which then read 0 (the structure is zero-initialised and the older library writes its own prefix)
-    if v != RTG_ABI_VERSION and not (os.environ.get("RTG_LIBRARY") and v == RTG_ABI_VERSION - 1 == 8):
+    # (no allowance for older dev variants under RTG_LIBRARY any more: ABI 10 added entry points, which
+    # an older library does not export)
+    if v != RTG_ABI_VERSION:
         raise RtgError("librtg.so ABI version mismatch")
     if path is None:
         _lib = lib
@@ -251,8 +273,7 @@ def load_library(path: str | None = None):
 
 
 def loaded_abi() -> int:
-    """The ABI version of the library in use (RTG_ABI_VERSION, or a dev variant's one older: the scene
-    descriptor's layout is the same in ABI 8 and 9)."""
+    """The ABI version of the library in use (RTG_ABI_VERSION once it has loaded)."""
     try:
         return int(load_library().rtg_abi_version())
     except (RtgError, OSError):

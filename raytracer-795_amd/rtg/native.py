@@ -41,6 +41,9 @@ def load():
         lib.rtgh_render_scene.restype = C.c_int32
         lib.rtgh_render_scene_multi.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_uint64, C.c_char_p]
         lib.rtgh_render_scene_multi.restype = C.c_int32
+        lib.rtgh_render_scene_progressive.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32,
+                                                      C.c_double]
+        lib.rtgh_render_scene_progressive.restype = C.c_int32
         lib.rtgh_read_image.argtypes = [C.c_char_p, C.POINTER(A.PF), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.rtgh_read_image.restype = C.c_int32
         lib.rtgh_free_image.argtypes = [A.PF]
@@ -117,6 +120,14 @@ def render_scene(xml_path: str, device: int = 0, seed: int = 0x5EED2026, out_dir
     lib = load()
     _check(lib.rtgh_render_scene_multi(xml_path.encode(), device, num_devices, seed,
                                        out_dir.encode() if out_dir else None))
+
+
+def render_scene_progressive(xml_path: str, step: int, target_error: float = 0.0, device: int = 0,
+                             seed: int = 0x5EED2026, out_dir: str | None = None):
+    """rtgh_render_scene_progressive: rounds of `step` samples per camera, files rewritten each round."""
+    lib = load()
+    _check(lib.rtgh_render_scene_progressive(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None,
+                                             int(step), float(target_error)))
 
 
 def _struct(s) -> dict:

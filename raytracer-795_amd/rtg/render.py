@@ -34,11 +34,22 @@ class Renderer:
         A.check(self.lib.rtg_scene_create_ex(C.byref(desc), int(device), C.byref(bo), C.byref(h)), self.lib)
         self.handle = h
         self.device = device
+        self._frames = []
 
     def close(self):
         if getattr(self, "handle", None):
+            for f in list(getattr(self, "_frames", ())):      # a scene with live frames refuses to go
+                f.close()
             self.lib.rtg_scene_destroy(self.handle)
             self.handle = None
+
+    def frame(self, camera: Camera | int = 0, first_sample: int = 0, sample_count: int = 0, moments: bool = False,
+              **kw) -> "Frame":
+        """A progressive frame of `camera` (rtg_frame): samples first_sample ..
+        first_sample + sample_count - 1 of its num_samples (0 = through the last), added in chunks
+        with Frame.add; `kw` are the render options, fixed for the frame's life."""
+        cam = self.scene.cameras[camera] if isinstance(camera, int) else camera
+        return Frame(self, cam, first_sample, sample_count, moments, self.opts(**kw))
 
     def __del__(self):
         try:
@@ -146,17 +157,6 @@ def hits_to_dict(hits, n: int) -> dict:
     return {"full": raw[:, 0].copy(), "object": raw[:, 1].copy(), "prim": raw[:, 2].copy(),
             "material": raw[:, 3].copy(), "t": f[:, 4].copy(), "point": f[:, 5:8].copy(),
             "normal": f[:, 8:11].copy()}
-
-
-def _bvh(fn, handle, obj):
-    npr, nn = C.c_int32(), C.c_int32()
-    A.check(fn(handle, obj, C.byref(npr), C.byref(nn), None, None, None))
-    perm = np.zeros(max(npr.value, 1), np.int32)
-    nodes = np.zeros((max(nn.value, 1), 4), np.int32)
-    boxes = np.zeros((max(nn.value, 1), 6), np.float32)
-    A.check(fn(handle, obj, None, None, perm.ctypes.data_as(A.PI), nodes.ctypes.data_as(A.PI),
-               boxes.ctypes.data_as(A.PF)))
-    return perm[:npr.value], nodes[:nn.value], boxes[:nn.value]
 
 
 # ---------------------------------------------------------------------------- Image
@@ -306,3 +306,106 @@ def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed
             if tm is not None:
                 written.append(save_image(tonemapped_name(name), tm))
     return written
+
+
+def _bvh(fn, handle, obj):
+    npr, nn = C.c_int32(), C.c_int32()
+    A.check(fn(handle, obj, C.byref(npr), C.byref(nn), None, None, None))
+    perm = np.zeros(max(npr.value, 1), np.int32)
+    nodes = np.zeros((max(nn.value, 1), 4), np.int32)
+    boxes = np.zeros((max(nn.value, 1), 6), np.float32)
+    A.check(fn(handle, obj, None, None, perm.ctypes.data_as(A.PI), nodes.ctypes.data_as(A.PI),
+               boxes.ctypes.data_as(A.PF)))
+    return perm[:npr.value], nodes[:nn.value], boxes[:nn.value]
+
+
+class Frame:
+    """One camera's resumable accumulator on the GPU (rtg_frame).  Any chunking of the samples
+    resolves to the same bits; over the whole camera that is Renderer.render's image.
+
+        with r.frame(0, moments=True) as f:
+            f.add(16)
+            while f.samples_done < total and f.error()["mean_sem"] > tol: f.add(16)
+            img = f.resolve()
+    """
+
+    def __init__(self, renderer: Renderer, cam: Camera, first_sample: int, sample_count: int, moments: bool, opts):
+        self.lib = renderer.lib
+        self.renderer = renderer
+        self.camera = cam
+        self.opts = opts
+        self.has_moments = bool(moments)
+        self.handle = None
+        fo = A.FrameOpts(int(first_sample), int(sample_count), int(self.has_moments), 0)
+        cd = cam.desc()
+        h = C.c_void_p()
+        A.check(self.lib.rtg_frame_create(renderer.handle, C.byref(cd), C.byref(opts), C.byref(fo), C.byref(h)),
+                self.lib)
+        self.handle = h
+        self.rows = self.lib.rtg_shard_rows(cam.ny, opts.row_offset, opts.row_stride, opts.row_block)
+        renderer._frames.append(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.rtg_frame_destroy(self.handle)
+            self.handle = None
+            if self in self.renderer._frames:
+                self.renderer._frames.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def add(self, n: int, stream: int = 0) -> int:
+        """Trace the next n samples of every owned pixel; returns samples_done."""
+        A.check(self.lib.rtg_frame_add_samples(self.handle, int(n), C.c_void_p(stream)), self.lib)
+        return self.samples_done
+
+    @property
+    def samples_done(self) -> int:
+        return int(self.lib.rtg_frame_samples_done(self.handle))
+
+    def resolve(self) -> np.ndarray:
+        rows = self.rows if self.opts.compact_rows else self.camera.ny
+        out = np.empty((rows, self.camera.nx, 3), np.float32)
+        A.check(self.lib.rtg_frame_resolve(self.handle, out.ctypes.data_as(A.PF)), self.lib)
+        return out
+
+    def resolve_device(self, out_ptr: int, stream: int = 0):
+        A.check(self.lib.rtg_frame_resolve_device(self.handle, C.c_void_p(out_ptr), C.c_void_p(stream)), self.lib)
+
+    def moments(self):
+        """(mean, variance) of the samples' luminance per owned pixel, (rows_owned, nx) float32 each."""
+        mean = np.empty((self.rows, self.camera.nx), np.float32)
+        var = np.empty_like(mean)
+        A.check(self.lib.rtg_frame_moments(self.handle, mean.ctypes.data_as(A.PF), var.ctypes.data_as(A.PF)), self.lib)
+        return mean, var
+
+    def error(self) -> dict:
+        e = A.FrameError()
+        A.check(self.lib.rtg_frame_error_stats(self.handle, C.byref(e)), self.lib)
+        return {k: getattr(e, k) for k, _ in A.FrameError._fields_}
+
+    def state(self) -> dict:
+        """A checkpoint for restore(): samples_done, the raw sums and (with moments) mean / M2."""
+        sums = np.zeros((self.rows, self.camera.nx, 3), np.float32)
+        mom = np.zeros((self.rows, self.camera.nx, 2), np.float32) if self.has_moments else None
+        A.check(self.lib.rtg_frame_get_state(self.handle, sums.ctypes.data_as(A.PF),
+                                             None if mom is None else mom.ctypes.data_as(A.PF)), self.lib)
+        return {"samples_done": self.samples_done, "sums": sums, "moments": mom}
+
+    def restore(self, state: dict):
+        sums = np.ascontiguousarray(state["sums"], np.float32)
+        mom = None if state.get("moments") is None else np.ascontiguousarray(state["moments"], np.float32)
+        if sums.size != self.rows * self.camera.nx * 3 or (mom is not None and mom.size != self.rows * self.camera.nx * 2):
+            raise ValueError("frame state of another size")
+        A.check(self.lib.rtg_frame_set_state(self.handle, int(state["samples_done"]), sums.ctypes.data_as(A.PF),
+                                             None if mom is None else mom.ctypes.data_as(A.PF)), self.lib)
