@@ -521,7 +521,7 @@ typedef struct rtg_frame_opts {
     int32_t first_sample;    /* first index of the camera's num_samples that this frame covers */
     int32_t sample_count;    /* how many it covers; 0 = through the last one */
     int32_t moments;         /* 1: keep a running mean and M2 of each pixel's sample luminance */
-    int32_t pad;
+    int32_t order;           /* sample order (ABI 10 additions below): 0 = index order, 1 = spread */
 } rtg_frame_opts;
 /* Error estimate over the owned pixels.  Y = (0.2126 R + 0.7152 G) + 0.0722 B of a sample, 0 when
    negative or not finite; per pixel, variance = M2 / (n - 1) (0 for n < 2) and the standard error
@@ -557,6 +557,56 @@ int32_t rtg_frame_error_stats(rtg_frame* frame, rtg_frame_error* out);
 int32_t rtg_frame_get_state(rtg_frame* frame, float* sums_out, float* moments_out);
 int32_t rtg_frame_set_state(rtg_frame* frame, int32_t samples_done, const float* sums, const float* moments);
 int32_t rtg_frame_destroy(rtg_frame* frame);
+
+/* ---- ABI 10 additions: adaptive sampling ------------------------------------
+   Additive: the version stays 10, no struct grows (rtg_frame_opts.order was its pad).
+
+   Sample order.  The camera's samples are stratified row by row (sample k sits in cell (k mod g,
+   k / g) of a g x g grid), so a prefix in index order covers the first sub-pixel rows only.  With
+   order 1, position j of a frame traces sample (j * m) mod n, n = num_samples: m = 1 for n <= 2,
+   else the smallest m >= max(1, (n * 618034 + 500000) / 1000000) (64-bit integers) with
+   gcd(m, n) = 1 -- a bijection of [0, n) whose prefixes are spread over the pixel.  first_sample,
+   sample_count and samples_done then count positions.  Sample k itself is the same ray tree (jitter
+   cell and random draws are keyed by pixel and sample index); the sums and the moments run in
+   position order, so an order-1 frame equals the same samples summed in that order, not rtg_render
+   bit for bit.  n > 32768 with order 1: RTG_ERR_UNSUPPORTED; an order other than 0 / 1: RTG_ERR_INVALID.
+   rtg_sample_order_index returns the sample index of `position` (negative status on bad arguments).
+
+   Retirement.  A pixel of a frame is active or retired; retirement is monotone (only
+   rtg_frame_set_state, which makes every pixel active again, and rtg_frame_set_retired undo it).
+   Every active pixel holds exactly samples_done samples; a retired pixel keeps the count it had when
+   it was retired.  rtg_frame_add_samples traces the next `count` positions of the active pixels
+   only (rtg_last_render_stats.primary_rays = active x count; no active pixel: nothing is traced,
+   RTG_OK) and advances samples_done.  resolve divides each pixel by its own count (0 samples: 0),
+   rtg_frame_moments and rtg_frame_error_stats use each pixel's own n (rtg_frame_error.samples_done
+   stays the frame's).  get_state / set_state are unchanged: the counts and flags travel through
+   rtg_frame_sample_counts / rtg_frame_set_retired.  Storage: 4 B per owned pixel for count and flag
+   and 4 B for the active list, allocated by the first retirement; a frame that never retires
+   allocates nothing and launches what it did before. */
+typedef struct rtg_frame_adapt {
+    float rel_tol;           /* retire when sem <= max(abs_tol, rel_tol * mean luminance) ... */
+    float abs_tol;
+    int32_t min_samples;     /* ... and samples_done >= max(min_samples, 2) */
+    int32_t pad;
+} rtg_frame_adapt;
+int32_t rtg_sample_order_index(int32_t num_samples, int32_t order, int32_t position);
+/* Needs moments and samples_done >= 1.  Retires every active pixel with n = samples_done >=
+   max(min_samples, 2) and (double)var / (double)n <= thr * thr, var = M2 / (float)(n - 1) in float32
+   as rtg_frame_moments returns it, thr = fmax((double)abs_tol, (double)rel_tol * (double)mean) --
+   squared on purpose: no sqrt, so a float64 restatement decides identically.  Negative or non-finite
+   tolerances: RTG_ERR_INVALID.  *active_out (may be NULL): the active pixels left. */
+int32_t rtg_frame_retire(rtg_frame* frame, const rtg_frame_adapt* adapt, int32_t* active_out);
+/* Retires the active pixels whose byte of `retire` (host, rows_owned * nx, owned-row order) is not 0;
+   with or without moments, and also at samples_done == 0 (a region-of-interest render: a pixel
+   retired without samples resolves to 0). */
+int32_t rtg_frame_retire_mask(rtg_frame* frame, const uint8_t* retire, int32_t* active_out);
+int32_t rtg_frame_active_pixels(const rtg_frame* frame);
+/* Per owned pixel, owned-row order: the samples it holds and 1 / 0 for retired / active; either may
+   be NULL. */
+int32_t rtg_frame_sample_counts(rtg_frame* frame, int32_t* counts_out, uint8_t* retired_out);
+/* Restores counts and flags after rtg_frame_set_state: 0 <= counts[p] <= samples_done, and
+   counts[p] == samples_done for every pixel that is not retired. */
+int32_t rtg_frame_set_retired(rtg_frame* frame, const int32_t* counts, const uint8_t* retired);
 
 #ifdef __cplusplus
 }

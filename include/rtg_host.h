@@ -65,6 +65,13 @@ int32_t rtgh_render_scene_multi(const char* xml_path, int32_t device, int32_t nu
    return type; tests/test_frame_abi.py checks that this one is exported.) */
 extern int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
                                              int32_t step, double target_error);
+/* Progressive with adaptive sampling (rtg_frame_retire): frames in sample order 1 with
+   moments, rounds of `step` positions; after each round every pixel whose standard error is at most
+   rel_tol x its mean luminance, and that holds at least max(min_samples, 2) samples, is retired and
+   traced no further.  The round's line ends with ", active <pixels left>".  A camera ends with its last
+   active pixel or its last sample.  (`extern` as above.) */
+extern int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                          int32_t step, double rel_tol, int32_t min_samples);
 
 #ifdef __cplusplus
 }

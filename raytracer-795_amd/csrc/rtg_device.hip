@@ -1713,14 +1713,14 @@ DEV void tile_pixel(int t, int nx, int rows_owned, int th, int ts, int& x, int& 
     x = tw * c + (u3 - r * wb);
     k = sh * band + th * rt + r;
 }
-DEV void slot_pixel(const CameraDev& cam, const PassDev& ps, int slot, uint32_t& pixel, uint32_t& sample, int& x,
+template <class PS> DEV void slot_pixel(const CameraDev& cam, const PS& ps, int slot, uint32_t& pixel, uint32_t& sample, int& x,
                     int& y) {
     const int pl = idiv(slot, ps.ns), sl = slot - pl * ps.ns;
     int k;
-    tile_pixel(ps.p0 + pl, cam.nx, ps.rows_owned, ps.tile_h, ps.tile_s, x, k);
+    tile_pixel(pass_pixel(ps, ps.p0 + pl), cam.nx, ps.rows_owned, ps.tile_h, ps.tile_s, x, k);   // (pass_pixel / pass_sample, rtg_internal.h: an adaptive frame's active list and sample order)
     y = shard_row(k, ps.row_offset, ps.row_stride, ps.row_block);
     pixel = (uint32_t)(y * cam.nx + x);
-    sample = (uint32_t)(ps.s0 + sl);
+    sample = (uint32_t)pass_sample(ps, ps.s0 + sl);
 }
 DEV f3 background(const SceneView& sv, const CameraDev& cam, int row, int col, f3 dir) {   // Scene.cpp:413-435
     if (sv.env_light != -1) {
@@ -1742,7 +1742,7 @@ DEV f3 background(const SceneView& sv, const CameraDev& cam, int row, int col, f
 // Primary ray of sample slot i of the pass (Camera::getPrimaryRay / getSampleRay).  Level 0's
 // k_trace / k_shade / k_pt_shade compute it from the slot (same function, so bit-identical)
 // instead of storing a queued ray + RayMeta per primary ray and re-reading it twice.
-DEV void primary_ray(const CameraDev& cam, const PassDev& ps, uint64_t seed, int i, f3& o_out, f3& d_out,
+template <class PS> DEV void primary_ray(const CameraDev& cam, const PS& ps, uint64_t seed, int i, f3& o_out, f3& d_out,
                      float& time_out) {
     uint32_t pixel, sample;
     int x, y;
@@ -1820,10 +1820,10 @@ DEV void store_ray(const RayQ& q, int k, f3 o, f3 d, float time) {
 // GEN: the launch may generate primary rays: rays [0, nq) are queued, ray i >= nq is
 // primary_ray(slot gbase + i - nq) (level 0 of a pass: nq = 0, gbase = 0; a regenerating step of
 // the path tracer's stream schedule: the survivors of the previous step, then new camera samples).
-template <bool EXHAUSTIVE, bool STATS, bool GEN = false, bool TLAS = false>
+template <bool EXHAUSTIVE, bool STATS, bool GEN = false, bool TLAS = false, class PS = PassDev>
 __global__ void __launch_bounds__(kTraceBlock) RTG_TRACE_ATTR k_trace(const SceneView sv, const RayQ rays,
                                                        HitRec* __restrict__ hits, int n, Counters* ctr,
-                                                       const CameraDev cam, const PassDev ps, uint64_t seed,
+                                                       const CameraDev cam, const PS ps, uint64_t seed,
                                                        bool compact, int nq, int gbase) {
     __shared__ int s_stack[kLdsStack * kTraceBlock];
     __shared__ short s_tstack[TLAS ? kTlasStack * kTraceBlock : 1];
@@ -1916,8 +1916,8 @@ DEV void mirror_ray(const SceneView& sv, f3 dir, const Ret& ret, const MaterialD
 // One ray's shading step (Scene::RecursiveShading for the node) plus the level's compaction of
 // child rays and shadow queries.  Called by every thread of the block (it synchronises); lanes
 // with i >= n only take part in the compaction.  h / o / d / time / mt: the traced ray and its hit.
-template <bool FULL, bool SPOT, int BLOCK, bool TEX>
-DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed, int i,
+template <bool FULL, bool SPOT, int BLOCK, bool TEX, class PS>
+DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const PS& ps, uint64_t seed, int i,
                    int n, const HitIn& hin, const f3 o, const f3 d, const float time, const RayMeta& mt,
                    const NodePlanes& nodes, const ShadowPlanes& shadows, int* __restrict__ slist,
                    const RayQ& next_rays, RayMeta* __restrict__ next_meta, unsigned long long* qcount,
@@ -2134,7 +2134,7 @@ DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const P
 }
 
 // Level-0 ray of slot i (no ray buffer) or the queued ray i.
-DEV void level_ray(const CameraDev& cam, const PassDev& ps, uint64_t seed, const RayQ& rays, int i,
+template <class PS> DEV void level_ray(const CameraDev& cam, const PS& ps, uint64_t seed, const RayQ& rays, int i,
                    f3& o, f3& d, float& time) {
     if (rays.a == nullptr) primary_ray(cam, ps, seed, i, o, d, time);
     else load_ray(rays, i, o, d, time);
@@ -2156,8 +2156,8 @@ DEV RayMeta level_meta(const SceneView& sv, int level, const RayQ& rays, const R
 // nq = 0), else queued rays only -- separate instantiations, so a queued-only launch carries no
 // ray-generation live ranges.  A queued ray's level is lv_in[i] in a stream step (levels mixed in
 // one launch), else `level_in`; lv_out (when set) receives the children's levels.
-template <bool FULL, bool SPOT, int BLOCK = FULL ? 256 : kShadeBlock, bool TEX = FULL, bool GEN = false>
-__global__ void __launch_bounds__(BLOCK) RTG_SHADE_ATTR k_shade(const SceneView sv, const CameraDev cam, int level_in, const PassDev ps,
+template <bool FULL, bool SPOT, int BLOCK = FULL ? 256 : kShadeBlock, bool TEX = FULL, bool GEN = false, class PS = PassDev>
+__global__ void __launch_bounds__(BLOCK) RTG_SHADE_ATTR k_shade(const SceneView sv, const CameraDev cam, int level_in, const PS ps,
                                                uint64_t seed,
                                                const RayQ rays, const RayMeta* __restrict__ meta,
                                                const HitRec* __restrict__ hits, const NodePlanes nodes,
@@ -2231,8 +2231,8 @@ constexpr int kContrib = 0x200;   // NodeRec.kind: the vertex adds T (x) colour 
 // (separate instantiations, as k_shade).  A queued ray's level is lv_in[i] when the schedule
 // mixes levels in one launch (stream steps), else `level_in`; lv_out (when set) receives the
 // continuation's level.
-template <bool FULL, bool SPOT, int BRDF, bool GEN = false>
-__global__ void __launch_bounds__(kPtBlock) RTG_PT_SHADE_ATTR k_pt_shade(const SceneView sv, const CameraDev cam, int level_in, const PassDev ps,
+template <bool FULL, bool SPOT, int BRDF, bool GEN = false, class PS = PassDev>
+__global__ void __launch_bounds__(kPtBlock) RTG_PT_SHADE_ATTR k_pt_shade(const SceneView sv, const CameraDev cam, int level_in, const PS ps,
                                                   uint64_t seed, const RayQ rays,
                                                   const RayMeta* __restrict__ meta, const HitRec* __restrict__ hits,
                                                   PathRec* __restrict__ paths, const NodePlanes nodes,
@@ -2893,9 +2893,9 @@ constexpr int kAccPixWide = 256, kAccChunkWide = 16;
 // running mean and M2 of the samples' luminance (Welford, one sample at a time in index order, float32;
 // mom holds mean and M2 per owned pixel in `acc` order, mom_k0 = the samples they already cover).  The
 // colours are in LDS already, so the moments cost no further HBM reads of per-sample records.
-template <bool DEEP, int PIX, int CHUNK, bool MOM>
+template <bool DEEP, int PIX, int CHUNK, bool MOM, class PS>
 DEV void accumulate_body(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                         float* __restrict__ acc, const PassDev& ps, int nx, int mode, const NodePlanes& level2,
+                         float* __restrict__ acc, const PS& ps, int nx, int mode, const NodePlanes& level2,
                          float* __restrict__ mom, int mom_k0) {
     constexpr int kAccPix = PIX, kAccChunk = CHUNK, kAccStride = CHUNK + 1;
     __shared__ float sr[kAccPix * kAccStride], sg[kAccPix * kAccStride], sb[kAccPix * kAccStride];
@@ -2907,7 +2907,7 @@ DEV void accumulate_body(const SceneView& sv, const NodePlanes& level0, const No
     size_t p = 0;
     if (t < np) {
         int x, k;
-        tile_pixel(ps.p0 + p0 + t, nx, ps.rows_owned, ps.tile_h, ps.tile_s, x, k);
+        tile_pixel(pass_pixel(ps, ps.p0 + p0 + t), nx, ps.rows_owned, ps.tile_h, ps.tile_s, x, k);   // (§15: the active list)
         p = (size_t)k * nx + x;                 // acc is in natural owned-row order
         if (mode == 0) a = mk(acc[3 * p], acc[3 * p + 1], acc[3 * p + 2]);
         if (MOM && mom_k0 > 0) { mean = mom[2 * p]; m2 = mom[2 * p + 1]; }
@@ -2952,17 +2952,17 @@ DEV void accumulate_body(const SceneView& sv, const NodePlanes& level0, const No
         if (MOM) { mom[2 * p] = mean; mom[2 * p + 1] = m2; }
     }
 }
-template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk>
+template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk, class PS = PassDev>
 __global__ void __launch_bounds__(256) k_accumulate(const SceneView sv,
                                                     const NodePlanes level0, const NodePlanes level1, bool resolve,
-                                                    float* __restrict__ acc, const PassDev ps, int nx, int mode,
+                                                    float* __restrict__ acc, const PS ps, int nx, int mode,
                                                     const NodePlanes level2) {
     accumulate_body<DEEP, PIX, CHUNK, false>(sv, level0, level1, resolve, acc, ps, nx, mode, level2, nullptr, 0);
 }
-template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk>
+template <bool DEEP = false, int PIX = kAccPix, int CHUNK = kAccChunk, class PS = PassDev>
 __global__ void __launch_bounds__(256) k_accumulate_mom(const SceneView sv,
                                                         const NodePlanes level0, const NodePlanes level1, bool resolve,
-                                                        float* __restrict__ acc, const PassDev ps, int nx, int mode,
+                                                        float* __restrict__ acc, const PS ps, int nx, int mode,
                                                         const NodePlanes level2, float* __restrict__ mom, int mom_k0) {
     accumulate_body<DEEP, PIX, CHUNK, true>(sv, level0, level1, resolve, acc, ps, nx, mode, level2, mom, mom_k0);
 }
@@ -3027,6 +3027,132 @@ __global__ void __launch_bounds__(256) k_finalize(const float* __restrict__ acc,
     out[3 * pix] = r; out[3 * pix + 1] = g; out[3 * pix + 2] = b;
 }
 
+// ---- adaptive frames: per-pixel retirement ---------------------------------------
+// cnt: one word per owned pixel in `acc` order; kRetiredBit set = retired, keeping the count in the low
+// bits; an active pixel (word 0) holds the frame's `done` samples.
+DEV int pixel_count(unsigned c, int done) { return (c & kRetiredBit) ? (int)(c & ~kRetiredBit) : done; }
+
+// k_finalize with each pixel divided by its own count (1: the sum itself; 0: black)
+__global__ void __launch_bounds__(256) k_finalize_counts(const float* __restrict__ acc, const unsigned* __restrict__ cnt,
+                                                         float* __restrict__ out, int nx, int ny, int row_offset,
+                                                         int row_stride, int row_block, int done) {
+    int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= nx * ny) return;
+    int y = pix / nx, x = pix - y * nx;
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    const int k = shard_owned_index(y, row_offset, row_stride, row_block);
+    if (k >= 0) {
+        int pl = k * nx + x;
+        const int total = pixel_count(cnt[pl], done);
+        if (total > 0) { r = acc[3 * pl]; g = acc[3 * pl + 1]; b = acc[3 * pl + 2]; }
+        if (total > 1) { r = r / (float)total; g = g / (float)total; b = b / (float)total; }
+    }
+    out[3 * pix] = r; out[3 * pix + 1] = g; out[3 * pix + 2] = b;
+}
+
+// k_frame_error with each pixel's own n (a pixel without samples counts as mean 0, sem 0); the same
+// fixed reduction shape, k_frame_error_final combines the partials
+__global__ void __launch_bounds__(kErrBlock) k_frame_error_counts(const float* __restrict__ mom,
+                                                                 const unsigned* __restrict__ cnt, int npix, int done,
+                                                                 double* __restrict__ part) {
+    const int i = blockIdx.x * kErrBlock + threadIdx.x;
+    double mean = 0.0, sem = 0.0;
+    if (i < npix) {
+        const int n = pixel_count(cnt[i], done);
+        if (n >= 1) {
+            mean = (double)mom[2 * (size_t)i];
+            const float var = n >= 2 ? mom[2 * (size_t)i + 1] / (float)(n - 1) : 0.0f;
+            sem = sqrt((double)var / (double)n);
+        }
+    }
+    err_block_reduce(mean, sem, sem, part + 3 * (size_t)blockIdx.x);
+}
+
+// rtg_frame_retire: one lane per owned pixel; an active pixel (n = done >= 2 samples, checked by the
+// host) retires when var / n <= thr^2 in double, var = M2 / (n - 1) in float32 as rtg_frame_moments
+// returns it, thr = max(abs_tol, rel_tol * mean) -- squared, so no sqrt and a float64 restatement
+// decides identically (a NaN variance compares false: the pixel stays active).
+__global__ void __launch_bounds__(256) k_frame_retire(const float* __restrict__ mom, unsigned* __restrict__ cnt, int npix,
+                                                      int done, float rel_tol, float abs_tol) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix || (cnt[i] & kRetiredBit)) return;
+    const float mean = mom[2 * (size_t)i];
+    const float var = mom[2 * (size_t)i + 1] / (float)(done - 1);
+    const double thr = fmax((double)abs_tol, (double)rel_tol * (double)mean);
+    if ((double)var / (double)done <= thr * thr) cnt[i] = kRetiredBit | (unsigned)done;
+}
+__global__ void __launch_bounds__(256) k_frame_retire_mask(const unsigned char* __restrict__ mask,
+                                                           unsigned* __restrict__ cnt, int npix, int done) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix || (cnt[i] & kRetiredBit) || mask[i] == 0) return;
+    cnt[i] = kRetiredBit | (unsigned)done;
+}
+
+// The active list: tile-order indices t (tile_pixel) of the pixels not retired, ascending, so
+// neighbouring ordinals stay neighbouring pixels.  Three launches and no atomics (the list repeats bit
+// for bit): k_active_count leaves each block's number of active indices in part[block];
+// k_active_scan (one block) turns part[0 .. nb) into exclusive prefixes, kScanBlock partials per round
+// with a running carry, and leaves the total in part[nb]; k_active_scatter writes index t to
+// part[block] + (active lanes below it in the block) from the same ballots.
+DEV bool active_at(const unsigned* __restrict__ cnt, int t, int npix, const PassDev& ps, int nx) {
+    if (t >= npix) return false;
+    int x, k;
+    tile_pixel(t, nx, ps.rows_owned, ps.tile_h, ps.tile_s, x, k);
+    return !(cnt[(size_t)k * nx + x] & kRetiredBit);
+}
+__global__ void __launch_bounds__(kScanBlock) k_active_count(const unsigned* __restrict__ cnt, int npix, const PassDev ps,
+                                                            int nx, int* __restrict__ part) {
+    __shared__ int sw[kScanBlock / 64];
+    const int t = blockIdx.x * kScanBlock + threadIdx.x;
+    const unsigned long long m = __ballot(active_at(cnt, t, npix, ps, nx));
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int k = 0; k < kScanBlock / 64; k++) c += sw[k];
+        part[blockIdx.x] = c;
+    }
+}
+__global__ void __launch_bounds__(kScanBlock) k_active_scan(int* __restrict__ part, int nb) {
+    __shared__ int sw[kScanBlock / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < nb; base += kScanBlock) {
+        const int i = base + threadIdx.x;
+        const int v = i < nb ? part[i] : 0;
+        int s = v;                                   // inclusive scan inside the wave
+        for (int off = 1; off < 64; off <<= 1) {
+            const int u = __shfl_up(s, off, 64);
+            if (lane >= off) s += u;
+        }
+        if (lane == 63) sw[w] = s;
+        __syncthreads();
+        int woff = 0, tot = 0;
+        for (int k = 0; k < kScanBlock / 64; k++) {
+            if (k < w) woff += sw[k];
+            tot += sw[k];
+        }
+        if (i < nb) part[i] = carry + woff + (s - v);
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[nb] = carry;
+}
+__global__ void __launch_bounds__(kScanBlock) k_active_scatter(const unsigned* __restrict__ cnt, int npix, const PassDev ps,
+                                                              int nx, const int* __restrict__ part,
+                                                              int* __restrict__ active) {
+    __shared__ int sw[kScanBlock / 64];
+    const int t = blockIdx.x * kScanBlock + threadIdx.x;
+    const int w = threadIdx.x >> 6;
+    const bool a = active_at(cnt, t, npix, ps, nx);
+    const unsigned long long m = __ballot(a);
+    if ((threadIdx.x & 63) == 0) sw[w] = __popcll(m);
+    __syncthreads();
+    int woff = 0;
+    for (int k = 0; k < w; k++) woff += sw[k];
+    if (a) active[part[blockIdx.x] + woff + __popcll(m & __lanemask_lt())] = t;
+}
+
 // Multi-GPU gather: frame row y comes from the shard that owns it, at that shard's compact row
 // index (the rows of every shard are stacked in `recv` in rank order).
 __global__ void __launch_bounds__(256) k_place_rows(const float* __restrict__ recv, float* __restrict__ frame, int nx,
@@ -3071,38 +3197,57 @@ __global__ void __launch_bounds__(256) k_hit_details(const SceneView sv, const R
 // ------------------------------------------------------------------ launchers
 static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 
-void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
-                  hipStream_t st, const CameraDev* gen_cam, const PassDev* gen_ps, uint64_t seed, bool compact,
-                  int nq, int gbase) {
+// The launchers that hand a pass to the kernels are templates over the pass type: PassDev (rtg_render, plain
+// frames), or PassDevA (an adaptive frame), which falls back to PassDev when it is plain().
+template <class PS>
+static void launch_trace_t(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
+                           hipStream_t st, const CameraDev* gen_cam, const PS* gen_ps, uint64_t seed, bool compact,
+                           int nq, int gbase) {
     if (n <= 0) return;
     dim3 g(nblk(n, kTraceBlock)), b(kTraceBlock);
     const CameraDev cam = gen_cam ? *gen_cam : CameraDev{};
-    const PassDev ps = gen_ps ? *gen_ps : PassDev{};
+    const PS ps = gen_ps ? *gen_ps : PS{};
     const bool tl = sv.tlas_root >= 0;
 #define RTG_TRACE(EX, STA, GEN)                                                                                   \
     do {                                                                                                          \
-        if (tl) hipLaunchKernelGGL((k_trace<EX, STA, GEN, true>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase); \
-        else hipLaunchKernelGGL((k_trace<EX, STA, GEN, false>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase); \
+        if (tl) hipLaunchKernelGGL((k_trace<EX, STA, GEN, true, PS>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase); \
+        else hipLaunchKernelGGL((k_trace<EX, STA, GEN, false, PS>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase); \
     } while (0)
     if (gen_cam) {   // primary rays generated in the kernel (rays unused)
-        if (exhaustive) hipLaunchKernelGGL((k_trace<true, false, true, false>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase);
+        if (exhaustive) hipLaunchKernelGGL((k_trace<true, false, true, false, PS>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase);
         else if (ctr) RTG_TRACE(false, true, true);
         else RTG_TRACE(false, false, true);
         return;
     }
-    if (exhaustive) hipLaunchKernelGGL((k_trace<true, false, false, false>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase);
-    else if (ctr) RTG_TRACE(false, true, false);
-    else RTG_TRACE(false, false, false);
+    if constexpr (std::is_same<PS, PassDev>::value) {     // queued rays only: the pass is not read
+        if (exhaustive) hipLaunchKernelGGL((k_trace<true, false, false, false>), g, b, 0, st, sv, rays, hits, n, ctr, cam, ps, seed, compact, nq, gbase);
+        else if (ctr) RTG_TRACE(false, true, false);
+        else RTG_TRACE(false, false, false);
+    }
 #undef RTG_TRACE
+}
+void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
+                  hipStream_t st, const CameraDev* gen_cam, const PassDev* gen_ps, uint64_t seed, bool compact,
+                  int nq, int gbase) {
+    launch_trace_t<PassDev>(sv, rays, hits, n, exhaustive, ctr, st, gen_cam, gen_ps, seed, compact, nq, gbase);
+}
+void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
+                  hipStream_t st, const CameraDev* gen_cam, const PassDevA* gen_ps, uint64_t seed, bool compact,
+                  int nq, int gbase) {
+    if (!gen_cam || !gen_ps || gen_ps->plain())
+        launch_trace_t<PassDev>(sv, rays, hits, n, exhaustive, ctr, st, gen_cam, gen_ps, seed, compact, nq, gbase);
+    else
+        launch_trace_t<PassDevA>(sv, rays, hits, n, exhaustive, ctr, st, gen_cam, gen_ps, seed, compact, nq, gbase);
 }
 __global__ void k_warm() {}
 void device_warm(hipStream_t st) { hipLaunchKernelGGL(k_warm, dim3(1), dim3(64), 0, st); }
 
-void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
-                  const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
-                  ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
-                  unsigned long long* qcount, int n, hipStream_t st,
-                  int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
+template <class PS>
+static void launch_shade_t(const SceneView& sv, const CameraDev& cam, int level, const PS& ps, uint64_t seed,
+                           const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
+                           ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
+                           unsigned long long* qcount, int n, hipStream_t st,
+                           int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
     if (n <= 0) return;
     dim3 g(nblk(n, kShadeBlock)), b(kShadeBlock);
     const NodePlanes np = node_planes(nodes, n);
@@ -3111,10 +3256,10 @@ void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const Pa
 #define RTG_SHADE(F, S, B, T, gr, bl)                                                                             \
     do {                                                                                                          \
         if (G)                                                                                                    \
-            hipLaunchKernelGGL((k_shade<F, S, B, T, true>), gr, bl, 0, st, sv, cam, level, ps, seed, rays, meta, hits, np, sp, \
+            hipLaunchKernelGGL((k_shade<F, S, B, T, true, PS>), gr, bl, 0, st, sv, cam, level, ps, seed, rays, meta, hits, np, sp, \
                                slist, next_rays, next_meta, qcount, n, nq, gbase, lv_in, lv_out); \
         else                                                                                                      \
-            hipLaunchKernelGGL((k_shade<F, S, B, T, false>), gr, bl, 0, st, sv, cam, level, ps, seed, rays, meta, hits, np, sp, \
+            hipLaunchKernelGGL((k_shade<F, S, B, T, false, PS>), gr, bl, 0, st, sv, cam, level, ps, seed, rays, meta, hits, np, sp, \
                                slist, next_rays, next_meta, qcount, n, nq, gbase, lv_in, lv_out); \
     } while (0)
     // full variants: SPOT = a spot or environment light (their libm code compiled in)
@@ -3126,6 +3271,26 @@ void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const Pa
     else if (sv.spot) RTG_SHADE(false, true, kShadeBlock, false, g, b);
     else RTG_SHADE(false, false, kShadeBlock, false, g, b);
 #undef RTG_SHADE
+}
+void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
+                  const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
+                  ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
+                  unsigned long long* qcount, int n, hipStream_t st,
+                  int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
+    launch_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, nodes, shadows, slist, next_rays, next_meta, qcount, n,
+                            st, gen, nq, gbase, lv_in, lv_out);
+}
+void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed,
+                  const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
+                  ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
+                  unsigned long long* qcount, int n, hipStream_t st,
+                  int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
+    if (ps.plain())
+        launch_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, nodes, shadows, slist, next_rays, next_meta,
+                                qcount, n, st, gen, nq, gbase, lv_in, lv_out);
+    else
+        launch_shade_t<PassDevA>(sv, cam, level, ps, seed, rays, meta, hits, nodes, shadows, slist, next_rays, next_meta,
+                                 qcount, n, st, gen, nq, gbase, lv_in, lv_out);
 }
 void launch_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, const unsigned* scount, NodeRec* nodes,
                    int n, int exhaustive, Counters* ctr, unsigned* nan_queries, hipStream_t st, bool whitted, int uni_from) {
@@ -3164,15 +3329,16 @@ void launch_pt_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist,
         else hipLaunchKernelGGL((k_shadow<false, false, false, true>), g, b, 0, st, sv, sp, false, sl, sc, np, nan_queries, ctr, uni_from, prl);
     }
 }
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
-                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
-                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
-                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
-                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
+template <class PS>
+static void launch_pt_shade_t(const SceneView& sv, const CameraDev& cam, int level, const PS& ps, uint64_t seed,
+                              const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
+                              ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
+                              unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
+                              const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
     if (n <= 0) return;
     dim3 g(nblk(n, kPtBlock)), b(kPtBlock);
 #define RTG_PT_LAUNCH1(F, S, B, G)                                                                                \
-    hipLaunchKernelGGL((k_pt_shade<F, S, B, G>), g, b, 0, st, sv, cam, level, ps, seed, rays, meta, hits, paths, \
+    hipLaunchKernelGGL((k_pt_shade<F, S, B, G, PS>), g, b, 0, st, sv, cam, level, ps, seed, rays, meta, hits, paths, \
                        node_planes(nodes, n), \
                        shadow_planes(shadows, n, sv.num_lights), slist, next_rays, next_meta, next_paths, qcount, n, \
                        nq, gbase, lv_in, lv_out, pr, ctr)
@@ -3194,6 +3360,26 @@ void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const
 #undef RTG_PT_LAUNCH
 #undef RTG_PT_LAUNCH1
 }
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
+                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
+                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
+                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
+                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
+    launch_pt_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, paths, nodes, shadows, slist, next_rays, next_meta,
+                               next_paths, qcount, n, st, gen, nq, gbase, lv_in, lv_out, pr, ctr);
+}
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed,
+                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
+                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
+                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
+                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
+    if (ps.plain())
+        launch_pt_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, paths, nodes, shadows, slist, next_rays,
+                                   next_meta, next_paths, qcount, n, st, gen, nq, gbase, lv_in, lv_out, pr, ctr);
+    else
+        launch_pt_shade_t<PassDevA>(sv, cam, level, ps, seed, rays, meta, hits, paths, nodes, shadows, slist, next_rays,
+                                    next_meta, next_paths, qcount, n, st, gen, nq, gbase, lv_in, lv_out, pr, ctr);
+}
 void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_nodes, const NodeRec* grand_nodes, int n,
                      int n_child, int n_grand, hipStream_t st) {
     if (n <= 0) return;
@@ -3212,29 +3398,31 @@ void launch_resolve_planes(const SceneView& sv, const NodePlanes& self, const No
     if (count <= 0) return;
     hipLaunchKernelGGL(k_resolve, dim3(nblk(count, 256)), dim3(256), 0, st, sv, self, child, count);
 }
-void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
+template <class PS>
+static void launch_accumulate_planes_t(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
+                                       float* acc, const PS& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
     if (ps.npass <= 0) return;
     const bool wide = !resolve || ps.ns <= kAccChunkWide;
     if (mom) {      // a frame with moments: the same shapes, the luminance moments continued in the same launch
         if (wide)
-            hipLaunchKernelGGL((k_accumulate_mom<false, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)),
+            hipLaunchKernelGGL((k_accumulate_mom<false, kAccPixWide, kAccChunkWide, PS>), dim3(nblk(ps.npass, kAccPixWide)),
                                dim3(256), 0, st, sv, level0, level1, resolve, acc, ps, nx, mode, NodePlanes{}, mom, mom_k0);
         else
-            hipLaunchKernelGGL(k_accumulate_mom<false>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, level0,
+            hipLaunchKernelGGL((k_accumulate_mom<false, kAccPix, kAccChunk, PS>), dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, level0,
                                level1, resolve, acc, ps, nx, mode, NodePlanes{}, mom, mom_k0);
         return;
     }
     if (wide)
-        hipLaunchKernelGGL((k_accumulate<false, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
+        hipLaunchKernelGGL((k_accumulate<false, kAccPixWide, kAccChunkWide, PS>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
                            0, st, sv, level0, level1, resolve, acc, ps, nx, mode, NodePlanes{});
     else
-        hipLaunchKernelGGL(k_accumulate<false>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, level0, level1,
+        hipLaunchKernelGGL((k_accumulate<false, kAccPix, kAccChunk, PS>), dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, level0, level1,
                            resolve, acc, ps, nx, mode, NodePlanes{});
 }
-void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
-                       const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
-                       const NodeRec* level2, int n2, float* mom, int mom_k0) {
+template <class PS>
+static void launch_accumulate_t(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
+                                const PS& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
+                                const NodeRec* level2, int n2, float* mom, int mom_k0) {
     if (ps.npass <= 0) return;
     NodeRec* l0 = const_cast<NodeRec*>(level0);
     const NodePlanes p0 = node_planes(l0, n0);
@@ -3243,20 +3431,42 @@ void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec
         const NodePlanes p2 = node_planes(const_cast<NodeRec*>(level2), n2);
         if (mom) {
             if (ps.ns <= kAccChunkWide)
-                hipLaunchKernelGGL((k_accumulate_mom<true, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)),
+                hipLaunchKernelGGL((k_accumulate_mom<true, kAccPixWide, kAccChunkWide, PS>), dim3(nblk(ps.npass, kAccPixWide)),
                                    dim3(256), 0, st, sv, p0, p1, true, acc, ps, nx, mode, p2, mom, mom_k0);
             else
-                hipLaunchKernelGGL(k_accumulate_mom<true>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1,
+                hipLaunchKernelGGL((k_accumulate_mom<true, kAccPix, kAccChunk, PS>), dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1,
                                    true, acc, ps, nx, mode, p2, mom, mom_k0);
         } else if (ps.ns <= kAccChunkWide)
-            hipLaunchKernelGGL((k_accumulate<true, kAccPixWide, kAccChunkWide>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
+            hipLaunchKernelGGL((k_accumulate<true, kAccPixWide, kAccChunkWide, PS>), dim3(nblk(ps.npass, kAccPixWide)), dim3(256),
                                0, st, sv, p0, p1, true, acc, ps, nx, mode, p2);
         else
-            hipLaunchKernelGGL(k_accumulate<true>, dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1, true, acc,
+            hipLaunchKernelGGL((k_accumulate<true, kAccPix, kAccChunk, PS>), dim3(nblk(ps.npass, kAccPix)), dim3(256), 0, st, sv, p0, p1, true, acc,
                                ps, nx, mode, p2);
     } else {
-        launch_accumulate_planes(sv, p0, p1, resolve && whitted, acc, ps, nx, mode, st, mom, mom_k0);
+        launch_accumulate_planes_t<PS>(sv, p0, p1, resolve && whitted, acc, ps, nx, mode, st, mom, mom_k0);
     }
+}
+void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
+                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
+    launch_accumulate_planes_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, mom, mom_k0);
+}
+void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
+                              float* acc, const PassDevA& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
+    if (ps.plain()) launch_accumulate_planes_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, mom, mom_k0);
+    else launch_accumulate_planes_t<PassDevA>(sv, level0, level1, resolve, acc, ps, nx, mode, st, mom, mom_k0);
+}
+void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
+                       const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
+                       const NodeRec* level2, int n2, float* mom, int mom_k0) {
+    launch_accumulate_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
+}
+void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
+                       const PassDevA& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
+                       const NodeRec* level2, int n2, float* mom, int mom_k0) {
+    if (ps.plain())
+        launch_accumulate_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
+    else
+        launch_accumulate_t<PassDevA>(sv, level0, level1, resolve, acc, ps, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
 }
 void launch_frame_error(const float* mom, int npix, int n, double* part, double* out, hipStream_t st) {
     const int nb = nblk(std::max(npix, 1), kErrBlock);
@@ -3269,6 +3479,35 @@ void launch_finalize(const float* acc, float* out, int nx, int ny, int row_offse
     if (n <= 0) return;
     hipLaunchKernelGGL(k_finalize, dim3(nblk(n, 256)), dim3(256), 0, st, acc, out, nx, ny, row_offset, row_stride,
                        row_block, total);
+}
+void launch_finalize_counts(const float* acc, const unsigned* cnt, float* out, int nx, int ny, int row_offset,
+                            int row_stride, int row_block, int done, hipStream_t st) {
+    int n = nx * ny;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_finalize_counts, dim3(nblk(n, 256)), dim3(256), 0, st, acc, cnt, out, nx, ny, row_offset,
+                       row_stride, row_block, done);
+}
+void launch_frame_error_counts(const float* mom, const unsigned* cnt, int npix, int done, double* part, double* out,
+                               hipStream_t st) {
+    const int nb = nblk(std::max(npix, 1), kErrBlock);
+    hipLaunchKernelGGL(k_frame_error_counts, dim3(nb), dim3(kErrBlock), 0, st, mom, cnt, npix, done, part);
+    hipLaunchKernelGGL(k_frame_error_final, dim3(1), dim3(kErrBlock), 0, st, part, nb, out);
+}
+void launch_frame_retire(const float* mom, unsigned* cnt, int npix, int done, float rel_tol, float abs_tol,
+                         hipStream_t st) {
+    if (npix <= 0) return;
+    hipLaunchKernelGGL(k_frame_retire, dim3(nblk(npix, 256)), dim3(256), 0, st, mom, cnt, npix, done, rel_tol, abs_tol);
+}
+void launch_frame_retire_mask(const unsigned char* mask, unsigned* cnt, int npix, int done, hipStream_t st) {
+    if (npix <= 0) return;
+    hipLaunchKernelGGL(k_frame_retire_mask, dim3(nblk(npix, 256)), dim3(256), 0, st, mask, cnt, npix, done);
+}
+void launch_active_list(const unsigned* cnt, int npix, const PassDev& ps, int nx, int* part, int* active,
+                        hipStream_t st) {
+    const int nb = nblk(std::max(npix, 1), kScanBlock);
+    hipLaunchKernelGGL(k_active_count, dim3(nb), dim3(kScanBlock), 0, st, cnt, npix, ps, nx, part);
+    hipLaunchKernelGGL(k_active_scan, dim3(1), dim3(kScanBlock), 0, st, part, nb);
+    hipLaunchKernelGGL(k_active_scatter, dim3(nb), dim3(kScanBlock), 0, st, cnt, npix, ps, nx, part, active);
 }
 void launch_place_rows(const float* recv, float* frame, int nx, int ny, int nranks, int block, const ShardPrefix& pre,
                        hipStream_t st) {

@@ -2500,7 +2500,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     long long npix_ll = (long long)rows_owned * cam->nx;
     if (npix_ll > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
     int npix = (int)npix_ll;
-    RenderTarget tg = target ? *target : RenderTarget{nullptr, nullptr, 0, cam->num_samples, 0}; const int total = tg.ns;   // samples per pixel of this call
+    RenderTarget tg = target ? *target : RenderTarget{nullptr, nullptr, 0, cam->num_samples, 0}; const int total = tg.ns; if (tg.active) npix = tg.nactive;   // total: samples per pixel of this call; npix: pixel ordinals (an adaptive frame: its active pixels, §15)
     if (cam->integrator != RTG_INTEGRATOR_REFERENCE && cam->integrator != RTG_INTEGRATOR_PATH)
         return fail(RTG_ERR_INVALID, "unknown integrator");
     const bool pt = cam->integrator == RTG_INTEGRATOR_PATH;
@@ -2587,15 +2587,15 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     // widest tiles (tile_h <= 8) below 2^31 pixels
     if ((long long)8 * cam->nx >= (1LL << 31)) return fail(RTG_ERR_UNSUPPORTED, "image wider than 2^28 pixels");
     tile_s = (int)std::min<long long>(tile_s, ((1LL << 31) - 1) / (8LL * cam->nx));
-    std::vector<PassDev> plist;
+    std::vector<PassDevA> plist;
     for (int p0 = 0; p0 < npix; p0 += np_pass)
         for (int s0 = 0; s0 < total; s0 += ns_chunk) {
-            PassDev ps;
+            PassDevA ps;
             ps.s0 = tg.s0 + s0; ps.ns = std::min(ns_chunk, total - s0);
             ps.p0 = p0; ps.npass = std::min(np_pass, npix - p0);
             ps.row_offset = off; ps.row_stride = stride; ps.rows_owned = rows_owned; ps.row_block = block;
-            ps.tile_h = tile_h;
-            ps.tile_s = tile_s;
+            ps.tile_h = tile_h; ps.active = tg.active;
+            ps.tile_s = tile_s; ps.ord_m = tg.ord_m; ps.ord_n = tg.ord_n;
             plist.push_back(ps);
         }
     const int nranges = npix > 0 ? (npix + np_pass - 1) / np_pass : 1;
@@ -2620,7 +2620,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
                                                                              : std::max(0, s->sv.max_depth) + 1;
     // enqueue trace / shade / shadow of the lane's current level and the count read-back
     auto enqueue_level = [&](Lane& ln) -> int {
-        const PassDev& ps = plist[ln.pass];
+        const PassDevA& ps = plist[ln.pass];
         const int level = ln.level;
         const int n = ln.counts[level];
         if ((int)ln.levels.size() < level + 2) ln.levels.resize(level + 2);
@@ -2684,7 +2684,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     };
     auto start_pass = [&](Lane& ln) -> int {
         ln.pass = ln.passes[ln.next_pass++];
-        const PassDev& ps = plist[ln.pass];
+        const PassDevA& ps = plist[ln.pass];
         const int n0 = ps.ns * ps.npass;
         int rc2;
         if ((rc2 = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc2;
@@ -2717,7 +2717,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
         return RTG_OK;
     };
     auto finish_pass = [&](Lane& ln) -> int {
-        const PassDev& ps = plist[ln.pass];
+        const PassDevA& ps = plist[ln.pass];
         const int level = ln.level;
         stt.max_level = std::max(stt.max_level, level);
         int rc2;
@@ -2827,11 +2827,11 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             if (pt && (rc = ln.lcnt.grow(sizeof(unsigned) * 2 * (size_t)nLb))) return rc;
             HIP_TRY(hipStreamWaitEvent(ln.st, e0, 0));
         }
-        PassDev F;
+        PassDevA F;
         F.s0 = tg.s0; F.ns = total; F.p0 = 0; F.npass = npix;
         F.row_offset = off; F.row_stride = stride; F.rows_owned = rows_owned; F.row_block = block;
-        F.tile_h = tile_h;
-        F.tile_s = tile_s;
+        F.tile_h = tile_h; F.active = tg.active;
+        F.tile_s = tile_s; F.ord_m = tg.ord_m; F.ord_n = tg.ord_n;
         long long cursor = 0, seg_end = 0, seg_slots = 0;
         double seg_node_bytes = 0.0;
         bool seg_closed = false;
@@ -3017,7 +3017,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
                         if (ln.step_g[j] > 0) {
                             const int mj = ln.step_m[j];
                             const NodePlanes l0 = {self.col + mj, self.pnt + mj, self.link + mj};
-                            PassDev P = F;
+                            PassDevA P = F;
                             P.p0 = ln.step_gb[j] / total;
                             P.npass = ln.step_g[j] / total;
                             if ((rc = timed_launch(ln, [&] {
@@ -3261,7 +3261,71 @@ struct rtg_frame {
     int rows_owned = 0, npix = 0;
     DBuf acc, mom;                           // 3 / 2 floats per owned pixel, owned-row order
     DBuf err;                                // error_stats: per-block partials + the 3 results (doubles)
+    // Adaptive sampling; nothing below is allocated before the first retirement.
+    int order = 0, ord_m = 0;                // sample order: position j traces sample (j * ord_m) % num_samples (0: j)
+    bool adaptive = false;                   // cnt / active exist: some call retired (or restored) pixels
+    int nactive = 0;                         // active pixels (npix while !adaptive)
+    DBuf cnt;                                // per owned pixel: kRetiredBit | samples kept, 0 while active
+    DBuf active;                             // the active pixels' tile-order indices, ascending
+    DBuf scan;                               // per-block counts of the list build + the total; mask staging
 };
+
+// The multiplier of sample order 1 (include/rtg.h): 1 for n <= 2, else the smallest m >= max(1, round
+// (0.618034 n)) coprime to n -- a golden-ratio stride, so consecutive positions land far apart in the
+// row-major strata and every prefix is spread over the pixel.
+static int order_multiplier(int n) {
+    if (n <= 2) return 1;
+    long long m = std::max(1LL, ((long long)n * 618034 + 500000) / 1000000);
+    auto gcd = [](long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; };
+    while (gcd(m, n) != 1) m++;
+    return (int)m;
+}
+constexpr int kOrderMaxSamples = 32768;      // (j * m) stays below 2^31
+
+// The pixel order of the frame's renders: render_impl's rule for tile_h / tile_s, which the active list
+// (tile-order indices) must share.
+static PassDev frame_tiles(const rtg_frame* f) {
+    const rtg_render_opts& o = f->opts;
+    const int stride = o.row_stride > 1 ? o.row_stride : 1, block = o.row_block > 1 ? o.row_block : 1;
+    PassDev ps{};
+    ps.row_offset = o.row_offset; ps.row_stride = stride; ps.rows_owned = f->rows_owned; ps.row_block = block;
+    ps.tile_h = stride > 1 && block < 8 ? (block >= 4 ? 4 : block >= 2 ? 2 : 1) : 8;
+    const int tile_s = o.tile_band > 0 ? std::min(o.tile_band, 1 << 12) : std::max(1, kBandRows / ps.tile_h);
+    ps.tile_s = (int)std::min<long long>(tile_s, ((1LL << 31) - 1) / (8LL * f->cam.nx));
+    return ps;
+}
+
+// First retirement of a frame: the count words (all active) and the list's buffers.
+static int frame_adapt_alloc(rtg_frame* f) {
+    if (f->adaptive) return RTG_OK;
+    const size_t np = std::max<size_t>(f->npix, 1);
+    const size_t nb = (np + kScanBlock - 1) / kScanBlock;
+    int rc;
+    if ((rc = f->cnt.grow(sizeof(unsigned) * np)) || (rc = f->active.grow(sizeof(int) * np)) ||
+        (rc = f->scan.grow(std::max(sizeof(int) * (nb + 1), np))))
+        return rc;
+    HIP_TRY(hipMemset(f->cnt.p, 0, sizeof(unsigned) * np));
+    if (f->done == 0) {      // a pixel retired without samples keeps defined (zero) sums and moments
+        HIP_TRY(hipMemset(f->acc.p, 0, sizeof(float) * 3 * np));
+        if (f->moments) HIP_TRY(hipMemset(f->mom.p, 0, sizeof(float) * 2 * np));
+    }
+    f->adaptive = true;
+    f->nactive = f->npix;
+    return RTG_OK;
+}
+
+// Rebuild the active list from the count words and read its length back.
+static int frame_rebuild_active(rtg_frame* f) {
+    const size_t nb = ((size_t)std::max(f->npix, 1) + kScanBlock - 1) / kScanBlock;
+    launch_active_list(f->cnt.as<unsigned>(), f->npix, frame_tiles(f), f->cam.nx, f->scan.as<int>(), f->active.as<int>(),
+                       nullptr);
+    HIP_TRY(hipGetLastError());
+    int n = 0;
+    HIP_TRY(hipMemcpy(&n, f->scan.as<int>() + nb, sizeof(int), hipMemcpyDeviceToHost));
+    if (n < 0 || n > f->npix) return fail(RTG_ERR_HIP, "active list count out of range");
+    f->nactive = n;
+    return RTG_OK;
+}
 
 // The scene of every live frame (one entry per frame): a scene stays while frames render through it.
 static std::mutex g_frames_mu;
@@ -3300,6 +3364,9 @@ int32_t rtg_frame_create(rtg_scene* s, const rtg_camera_desc* cam, const rtg_ren
         if (fo.first_sample < 0 || fo.first_sample >= cam->num_samples || fo.sample_count < 0 ||
             fo.sample_count > cam->num_samples - fo.first_sample)
             return fail(RTG_ERR_INVALID, "frame window outside the camera's samples");
+        if (fo.order != 0 && fo.order != 1) return fail(RTG_ERR_INVALID, "unknown sample order");
+        if (fo.order == 1 && cam->num_samples > kOrderMaxSamples)
+            return fail(RTG_ERR_UNSUPPORTED, "sample order 1 takes at most 32768 samples");
         const int rows = rtg_shard_rows(cam->ny, o.row_offset, stride, block);
         if ((long long)rows * cam->nx > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
         HIP_TRY(hipSetDevice(s->device));
@@ -3313,6 +3380,9 @@ int32_t rtg_frame_create(rtg_scene* s, const rtg_camera_desc* cam, const rtg_ren
         f->moments = fo.moments != 0;
         f->rows_owned = rows;
         f->npix = rows * cam->nx;
+        f->nactive = f->npix;
+        f->order = fo.order;
+        f->ord_m = fo.order == 1 ? order_multiplier(cam->num_samples) : 0;
         int rc = f->acc.grow(sizeof(float) * 3 * std::max<size_t>(f->npix, 1));
         if (!rc && f->moments) rc = f->mom.grow(sizeof(float) * 2 * std::max<size_t>(f->npix, 1));
         if (rc) { f->acc.release(); f->mom.release(); delete f; return rc; }
@@ -3329,6 +3399,7 @@ int32_t rtg_frame_destroy(rtg_frame* f) {
     if (!f) return RTG_OK;
     if (f->scene->device >= 0) (void)hipSetDevice(f->scene->device);
     f->acc.release(); f->mom.release(); f->err.release();
+    f->cnt.release(); f->active.release(); f->scan.release();
     {
         std::lock_guard<std::mutex> lk(g_frames_mu);
         const auto it = std::find(g_frame_scenes.begin(), g_frame_scenes.end(), f->scene);
@@ -3350,8 +3421,20 @@ int32_t rtg_frame_add_samples(rtg_frame* f, int32_t count, void* stream) {
         if (count <= 0) return fail(RTG_ERR_INVALID, "sample count must be positive");
         if (count > f->count - f->done) return fail(RTG_ERR_INVALID, "more samples than the frame's window has left");
         HIP_TRY(hipSetDevice(f->scene->device));
-        const RenderTarget tg{f->acc.as<float>(), f->moments ? f->mom.as<float>() : nullptr, f->first + f->done, count,
-                              f->done};
+        RenderTarget tg{f->acc.as<float>(), f->moments ? f->mom.as<float>() : nullptr, f->first + f->done, count,
+                        f->done};
+        tg.ord_m = f->ord_m; tg.ord_n = f->cam.num_samples;
+        if (f->adaptive) {                       // the active pixels only
+            if (f->nactive == 0) {               // nothing left to trace
+                rtg_render_stats none{};
+                none.devices = 1;
+                f->scene->stats = none;
+                f->done += count;
+                return RTG_OK;
+            }
+            tg.active = f->active.as<int>();
+            tg.nactive = f->nactive;
+        }
         const int rc = render_impl(f->scene, &f->cam, &f->opts, nullptr, (hipStream_t)stream, &tg);
         if (rc) {
             f->broken = true;
@@ -3379,7 +3462,14 @@ int32_t rtg_frame_resolve_device(rtg_frame* f, float* rgb_out_device, void* stre
         const hipStream_t st = (hipStream_t)stream;
         const rtg_render_opts& o = f->opts;
         // k_finalize divides when its count exceeds 1 (x / 1.0f is x)
-        if (o.compact_rows)
+        if (f->adaptive && o.compact_rows)       // retired pixels: each by its own count
+            launch_finalize_counts(f->acc.as<float>(), f->cnt.as<unsigned>(), rgb_out_device, f->cam.nx, f->rows_owned, 0,
+                                   1, 1, f->done, st);
+        else if (f->adaptive)
+            launch_finalize_counts(f->acc.as<float>(), f->cnt.as<unsigned>(), rgb_out_device, f->cam.nx, f->cam.ny,
+                                   o.row_offset, o.row_stride > 1 ? o.row_stride : 1, o.row_block > 1 ? o.row_block : 1,
+                                   f->done, st);
+        else if (o.compact_rows)
             launch_finalize(f->acc.as<float>(), rgb_out_device, f->cam.nx, f->rows_owned, 0, 1, 1, f->done, st);
         else
             launch_finalize(f->acc.as<float>(), rgb_out_device, f->cam.nx, f->cam.ny, o.row_offset,
@@ -3417,8 +3507,13 @@ int32_t rtg_frame_moments(rtg_frame* f, float* mean_out, float* variance_out) {
         HIP_TRY(hipSetDevice(f->scene->device));
         std::vector<float> m((size_t)2 * f->npix);
         if (f->npix) HIP_TRY(hipMemcpy(m.data(), f->mom.p, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
-        const int n = f->done;
+        std::vector<unsigned> c;
+        if (f->adaptive && f->npix) {
+            c.resize((size_t)f->npix);
+            HIP_TRY(hipMemcpy(c.data(), f->cnt.p, sizeof(unsigned) * c.size(), hipMemcpyDeviceToHost));
+        }
         for (int i = 0; i < f->npix; i++) {
+            const int n = !c.empty() && (c[i] & kRetiredBit) ? (int)(c[i] & ~kRetiredBit) : f->done;   // the pixel's own count
             if (mean_out) mean_out[i] = m[2 * (size_t)i];
             if (variance_out) variance_out[i] = n >= 2 ? m[2 * (size_t)i + 1] / (float)(n - 1) : 0.0f;
         }
@@ -3436,7 +3531,10 @@ int32_t rtg_frame_error_stats(rtg_frame* f, rtg_frame_error* out) {
         if ((rc = f->err.grow(sizeof(double) * 3 * (nb + 1)))) return rc;
         double* part = f->err.as<double>();
         double* res = part + 3 * nb;
-        launch_frame_error(f->mom.as<float>(), f->npix, f->done, part, res, nullptr);
+        if (f->adaptive)
+            launch_frame_error_counts(f->mom.as<float>(), f->cnt.as<unsigned>(), f->npix, f->done, part, res, nullptr);
+        else
+            launch_frame_error(f->mom.as<float>(), f->npix, f->done, part, res, nullptr);
         HIP_TRY(hipGetLastError());
         double h[3] = {0.0, 0.0, 0.0};
         HIP_TRY(hipMemcpy(h, res, sizeof h, hipMemcpyDeviceToHost));
@@ -3477,6 +3575,110 @@ int32_t rtg_frame_set_state(rtg_frame* f, int32_t samples_done, const float* sum
         }
         f->done = samples_done;
         f->broken = false;
+        if (f->adaptive) {                       // every pixel active again (rtg_frame_set_retired follows, if any)
+            f->cnt.release(); f->active.release(); f->scan.release();
+            f->adaptive = false;
+            f->nactive = f->npix;
+        }
+        return RTG_OK;
+    });
+}
+
+// ---- ABI 10 additions: sample order and per-pixel retirement
+int32_t rtg_sample_order_index(int32_t num_samples, int32_t order, int32_t position) {
+    if (num_samples < 1 || position < 0 || position >= num_samples) return fail(RTG_ERR_INVALID, "position outside the samples");
+    if (order == 0) return position;
+    if (order != 1) return fail(RTG_ERR_INVALID, "unknown sample order");
+    if (num_samples > kOrderMaxSamples) return fail(RTG_ERR_UNSUPPORTED, "sample order 1 takes at most 32768 samples");
+    return (int32_t)(((long long)position * order_multiplier(num_samples)) % num_samples);
+}
+
+int32_t rtg_frame_active_pixels(const rtg_frame* f) {
+    if (!f) return fail(RTG_ERR_INVALID, "null argument");
+    return f->nactive;
+}
+
+static int frame_usable(const rtg_frame* f) {
+    if (!f) return fail(RTG_ERR_INVALID, "null argument");
+    if (f->broken) return fail(RTG_ERR_INVALID, "frame state lost by a failed call: restore it with rtg_frame_set_state");
+    return RTG_OK;
+}
+
+int32_t rtg_frame_retire(rtg_frame* f, const rtg_frame_adapt* a, int32_t* active_out) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_ready(f, true);
+        if (rc) return rc;
+        if (!a) return fail(RTG_ERR_INVALID, "null argument");
+        if (!std::isfinite(a->rel_tol) || !std::isfinite(a->abs_tol) || a->rel_tol < 0.0f || a->abs_tol < 0.0f)
+            return fail(RTG_ERR_INVALID, "tolerances must be finite and not negative");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        if (f->done >= std::max(a->min_samples, 2) && f->nactive > 0) {
+            if ((rc = frame_adapt_alloc(f))) return rc;
+            launch_frame_retire(f->mom.as<float>(), f->cnt.as<unsigned>(), f->npix, f->done, a->rel_tol, a->abs_tol,
+                                nullptr);
+            HIP_TRY(hipGetLastError());
+            if ((rc = frame_rebuild_active(f))) { f->broken = true; return rc; }
+        }
+        if (active_out) *active_out = f->nactive;
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_retire_mask(rtg_frame* f, const uint8_t* retire, int32_t* active_out) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_usable(f);
+        if (rc) return rc;
+        if (!retire) return fail(RTG_ERR_INVALID, "null argument");
+        HIP_TRY(hipSetDevice(f->scene->device));
+        if (f->npix > 0) {
+            if ((rc = frame_adapt_alloc(f))) return rc;
+            // the mask is staged in the list build's scratch: the retirement reads it before the list is built
+            HIP_TRY(hipMemcpy(f->scan.p, retire, (size_t)f->npix, hipMemcpyHostToDevice));
+            launch_frame_retire_mask(f->scan.as<unsigned char>(), f->cnt.as<unsigned>(), f->npix, f->done, nullptr);
+            HIP_TRY(hipGetLastError());
+            if ((rc = frame_rebuild_active(f))) { f->broken = true; return rc; }
+        }
+        if (active_out) *active_out = f->nactive;
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_sample_counts(rtg_frame* f, int32_t* counts_out, uint8_t* retired_out) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_usable(f);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(f->scene->device));
+        std::vector<unsigned> c;
+        if (f->adaptive && f->npix) {
+            c.resize((size_t)f->npix);
+            HIP_TRY(hipMemcpy(c.data(), f->cnt.p, sizeof(unsigned) * c.size(), hipMemcpyDeviceToHost));
+        }
+        for (int i = 0; i < f->npix; i++) {
+            const bool r = !c.empty() && (c[i] & kRetiredBit);
+            if (counts_out) counts_out[i] = r ? (int32_t)(c[i] & ~kRetiredBit) : f->done;
+            if (retired_out) retired_out[i] = r ? 1 : 0;
+        }
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_set_retired(rtg_frame* f, const int32_t* counts, const uint8_t* retired) {
+    return guarded([&]() -> int32_t {
+        int rc = frame_usable(f);
+        if (rc) return rc;
+        if (!counts || !retired) return fail(RTG_ERR_INVALID, "null argument");
+        std::vector<unsigned> c((size_t)std::max(f->npix, 1), 0u);
+        for (int i = 0; i < f->npix; i++) {
+            if (counts[i] < 0 || counts[i] > f->done || (!retired[i] && counts[i] != f->done))
+                return fail(RTG_ERR_INVALID, "counts must be within samples_done, and equal to it for active pixels");
+            if (retired[i]) c[i] = kRetiredBit | (unsigned)counts[i];
+        }
+        HIP_TRY(hipSetDevice(f->scene->device));
+        if (f->npix > 0) {
+            if ((rc = frame_adapt_alloc(f))) return rc;
+            HIP_TRY(hipMemcpy(f->cnt.p, c.data(), sizeof(unsigned) * (size_t)f->npix, hipMemcpyHostToDevice));
+            if ((rc = frame_rebuild_active(f))) { f->broken = true; return rc; }
+        }
         return RTG_OK;
     });
 }

@@ -432,16 +432,26 @@ constexpr size_t kCarryBytes = 16;    // float4 per queued ray
 
 // Host-side launchers (rtg_device.hip) ------------------------------------------------
 struct LevelBuffers;
+struct PassDevA;      // a pass of an adaptive frame (below)
 // gen_cam / gen_ps non-null: level 0 (either integrator), rays are generated in the kernel
 // nq / gbase (with gen_cam): rays [0, nq) are queued, ray i >= nq is the primary ray of slot gbase + i - nq
 void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive,
                   Counters* ctr, hipStream_t st, const CameraDev* gen_cam = nullptr, const PassDev* gen_ps = nullptr,
+                  uint64_t seed = 0, bool compact = false, int nq = 0, int gbase = 0);
+// (the PassDevA overloads of the launchers: an adaptive frame's passes; a plain() one takes the PassDev kernels)
+void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive,
+                  Counters* ctr, hipStream_t st, const CameraDev* gen_cam, const PassDevA* gen_ps,
                   uint64_t seed = 0, bool compact = false, int nq = 0, int gbase = 0);
 // gen: 1 = rays i >= nq are primary rays of slots gbase + i - nq, 0 = queued only, -1 = a pass's level
 // (primaries iff rays.a is null); lv_in / lv_out: per-ray levels of a stream step (or null)
 void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed, const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
                   ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
                   unsigned long long* qcount, int n, hipStream_t st,
+                  int gen = -1, int nq = 0, int gbase = 0, const unsigned char* lv_in = nullptr,
+                  unsigned char* lv_out = nullptr);
+void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed, const RayQ rays,
+                  const RayMeta* meta, const HitRec* hits, NodeRec* nodes, ShadowRec* shadows, int* slist,
+                  const RayQ next_rays, RayMeta* next_meta, unsigned long long* qcount, int n, hipStream_t st,
                   int gen = -1, int nq = 0, int gbase = 0, const unsigned char* lv_in = nullptr,
                   unsigned char* lv_out = nullptr);
 // the bottom-up step and the accumulation on explicit node planes (stream schedule: a step's nodes
@@ -456,6 +466,23 @@ struct RenderTarget {
     float* mom;       // mean and M2 of the samples' luminance, 2 per owned pixel, or null
     int s0, ns;       // the window of the camera's samples this call traces
     int have;         // samples already in acc / mom
+    // Adaptive frames.  active: the frame's active pixels as ascending tile-order
+    // indices (device; null = every owned pixel), nactive of them: the render loop then runs over
+    // pixel ordinals [0, nactive) and the kernels look the pixel up (PassDevA::active).  s0 / ns / have
+    // count positions of the sample order: position j traces sample (j * ord_m) % ord_n (ord_m 0: j).
+    const int* active = nullptr;
+    int nactive = 0;
+    int ord_m = 0, ord_n = 1;
+};
+// A pass of an adaptive frame: PassDev plus the active list (pixel ordinal p0 + i is the pixel at tile-order
+// index active[p0 + i]; null: the ordinal itself) and the sample order.  The kernels that turn a slot into
+// a pixel and a sample are templates over the pass type, so the instantiations rtg_render and plain frames
+// launch (PassDev) carry neither the fields nor the branches: the launchers fall back to them whenever a
+// PassDevA has no list and the identity order.
+struct PassDevA : PassDev {
+    const int* active = nullptr;
+    int ord_m = 0, ord_n = 1;
+    bool plain() const { return !active && !ord_m; }
 };
 
 // mom (a frame's moments, or null): mean and M2 of each pixel's sample luminance (2 floats per owned
@@ -463,12 +490,20 @@ struct RenderTarget {
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
                               float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
                               int mom_k0 = 0);
+void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
+                              float* acc, const PassDevA& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
+                              int mom_k0 = 0);
 void launch_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, const unsigned* scount, NodeRec* nodes,
                    int n, int exhaustive, Counters* ctr, unsigned* nan_queries, hipStream_t st, bool whitted = true, int uni_from = INT_MAX);  // uni_from: first camera-sample node (wave-uniform walk)
 // the path tracer's queries: one launch per light, in light order (PtRad)
 void launch_pt_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, NodeRec* nodes, int n, int exhaustive,
                       Counters* ctr, unsigned* nan_queries, hipStream_t st, int uni_from, const PtRad& pr);
 void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
+                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
+                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
+                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
+                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr = nullptr);
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed,
                      const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
                      ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
                      unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
@@ -484,6 +519,9 @@ void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_n
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
                        const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
                        const NodeRec* level2 = nullptr, int n2 = 0, float* mom = nullptr, int mom_k0 = 0);
+void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
+                       const PassDevA& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
+                       const NodeRec* level2 = nullptr, int n2 = 0, float* mom = nullptr, int mom_k0 = 0);
 // A frame's error figures (rtg_frame_error_stats): per-block double partials of the per-pixel mean and
 // standard error (3 doubles per block of 256 pixels in `part`: sum of means, sum of sems, max sem),
 // combined by one block into out[0..2] (sums, max) -- no atomics, so the figures repeat
@@ -491,6 +529,27 @@ constexpr int kErrBlock = 256;
 void launch_frame_error(const float* mom, int npix, int n, double* part, double* out, hipStream_t st);
 void launch_finalize(const float* acc, float* out, int nx, int ny, int row_offset, int row_stride, int row_block, int total,
                      hipStream_t st);
+// Adaptive frames.  cnt: one word per owned pixel in `acc` order -- kRetiredBit set
+// once the pixel is retired, the low bits then hold the samples it keeps; an active pixel's word is 0
+// (it holds the frame's samples_done).
+constexpr unsigned kRetiredBit = 0x80000000u;
+constexpr int kScanBlock = 256;
+// counts-aware forms of launch_finalize / launch_frame_error: each pixel by its own count (`done` for
+// the active ones)
+void launch_finalize_counts(const float* acc, const unsigned* cnt, float* out, int nx, int ny, int row_offset,
+                            int row_stride, int row_block, int done, hipStream_t st);
+void launch_frame_error_counts(const float* mom, const unsigned* cnt, int npix, int done, double* part, double* out,
+                               hipStream_t st);
+// retire the active pixels that pass (double)var / n <= thr^2, thr = max(abs_tol, rel_tol * mean), n = done
+void launch_frame_retire(const float* mom, unsigned* cnt, int npix, int done, float rel_tol, float abs_tol,
+                         hipStream_t st);
+// retire the active pixels whose byte of `mask` (device, owned-row order) is not 0
+void launch_frame_retire_mask(const unsigned char* mask, unsigned* cnt, int npix, int done, hipStream_t st);
+// The active list: the tile-order indices t in [0, npix) of the pixels not retired, ascending, and their
+// number in part[nblk(npix, kScanBlock)] (part: one int per block of kScanBlock indices + 1).  Ballot
+// prefixes, per-block counts, a scan of the counts, a scatter: no atomics, so the list repeats.
+void launch_active_list(const unsigned* cnt, int npix, const PassDev& ps, int nx, int* part, int* active,
+                        hipStream_t st);
 void launch_hit_details(const SceneView& sv, const RayQ rays, const HitRec* hits, struct ::rtg_hit* out,
                         const int* orig_prim, int n, hipStream_t st);
 
@@ -651,6 +710,15 @@ __device__ inline void queue_slots(bool split, bool has0, bool has1, unsigned st
     idx0 = (int)((unsigned)s_base + s_wc[w] + coff);
     idx1 = split ? (int)((unsigned)s_base + s_w1[w] + __popcll(m2 & lt)) : idx0 + (has0 ? 1 : 0);
     sb = (unsigned)(s_base >> 32) + s_ws[w];
+}
+
+// Pixel ordinal -> tile-order index and position -> sample index of a pass (slot_pixel, accumulate_body):
+// the identity for a PassDev; an adaptive frame's pass looks them up, wave-uniform branches.
+__device__ __forceinline__ int pass_pixel(const PassDev&, int ordinal) { return ordinal; }
+__device__ __forceinline__ int pass_sample(const PassDev&, int position) { return position; }
+__device__ __forceinline__ int pass_pixel(const PassDevA& ps, int ordinal) { return ps.active ? ps.active[ordinal] : ordinal; }
+__device__ __forceinline__ int pass_sample(const PassDevA& ps, int position) {
+    return ps.ord_m ? (int)(((unsigned)position * (unsigned)ps.ord_m) % (unsigned)ps.ord_n) : position;
 }
 
 // Luminance of a colour as the tone mapper and a frame's moments (§14) define it:

@@ -15,6 +15,12 @@
 // pixels' luminance and their mean luminance is printed.  --target-error E stops a camera after the first
 // round with mean_sem <= E x mean_luminance; without it (or with E = 0) the render runs to NumSamples and
 // the files equal those of a run without --progressive, byte for byte.  One GPU only.
+//
+//   rtg_cli scene.xml --progressive K --adaptive REL [--min-samples M] ...
+//
+// --adaptive REL (with --progressive) samples adaptively: after each round the pixels whose standard error is
+// at most REL x their mean luminance (and that hold at least M samples, default 2) are retired and traced no
+// further; the round's line also reports the active pixels, and a camera ends with its last active pixel.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,7 +32,9 @@ int main(int argc, char** argv) {
     const char* out_dir = nullptr;
     int device = 0, devices = 0, progressive = 0;
     bool have_progressive = false, have_target = false;
-    double target_error = 0.0;
+    double target_error = 0.0, adaptive = 0.0;
+    bool have_adaptive = false, have_min = false;
+    int min_samples = 2;
     unsigned long long seed = 0x5EED2026ull;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
@@ -35,12 +43,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--out-dir") && i + 1 < argc) out_dir = argv[++i];
         else if (!strcmp(argv[i], "--progressive") && i + 1 < argc) { progressive = atoi(argv[++i]); have_progressive = true; }
         else if (!strcmp(argv[i], "--target-error") && i + 1 < argc) { target_error = atof(argv[++i]); have_target = true; }
+        else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive = atof(argv[++i]); have_adaptive = true; }
+        else if (!strcmp(argv[i], "--min-samples") && i + 1 < argc) { min_samples = atoi(argv[++i]); have_min = true; }
         else if (argv[i][0] == '-') { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         else xml = argv[i];
     }
     if (!xml) {
         fprintf(stderr, "usage: %s scene.xml [--device N] [--devices G] [--seed S] [--out-dir DIR] "
-                        "[--progressive K [--target-error E]]\n", argv[0]);
+                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]]]\n", argv[0]);
         return 2;
     }
     if (have_progressive && devices > 0) {
@@ -51,7 +61,14 @@ int main(int argc, char** argv) {
         fprintf(stderr, "rtg_cli: --progressive needs K >= 1, --target-error needs --progressive and E >= 0\n");
         return 2;
     }
-    const int rc = have_progressive ? rtgh_render_scene_progressive(xml, device, seed, out_dir, progressive, target_error)
+    if ((have_adaptive && (!have_progressive || have_target || !(adaptive >= 0.0) || !(adaptive <= 3.0e38))) ||
+        (have_min && (!have_adaptive || min_samples < 1))) {
+        fprintf(stderr, "rtg_cli: --adaptive needs --progressive (without --target-error) and REL >= 0, "
+                        "--min-samples needs --adaptive and M >= 1\n");
+        return 2;
+    }
+    const int rc = have_adaptive ? rtgh_render_scene_adaptive(xml, device, seed, out_dir, progressive, adaptive, min_samples)
+                 : have_progressive ? rtgh_render_scene_progressive(xml, device, seed, out_dir, progressive, target_error)
                                     : rtgh_render_scene_multi(xml, device, devices, seed, out_dir);
     if (rc != RTG_OK) {
         fprintf(stderr, "rtg_cli: %s\n", rtgh_last_error());

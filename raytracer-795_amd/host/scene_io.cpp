@@ -1217,4 +1217,61 @@ int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint
     });
 }
 
+// The progressive loop with adaptive sampling: frames in sample order 1 with moments, rounds
+// of `step` positions; after each round the pixels whose standard error is at most rel_tol x their mean
+// luminance (and that hold at least min_samples) are retired and traced no further.  A camera ends with
+// its last active pixel or its last sample.
+int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                   int32_t step, double rel_tol, int32_t min_samples) {
+    return guarded([&]() -> int32_t {
+        if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
+        if (!(rel_tol >= 0.0) || !(rel_tol <= 3.0e38)) return fail(RTG_ERR_INVALID, "adaptive tolerance must be finite and not negative");
+        rtgh_scene* sc = nullptr;
+        int rc = rtgh_parse_xml(xml_path, &sc);
+        if (rc) return rc;
+        rtg_scene* gpu = nullptr;
+        rtg_build_opts bo{};
+        bo.bvh_builder = RTG_BVH_AUTO;
+        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
+        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
+        printf("BVH construction complete.\n");
+        for (const CamData& c : sc->cameras) {
+            std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
+            rtg_render_opts o{};
+            o.seed = seed;
+            rtg_frame_opts fo{};
+            fo.moments = 1;
+            fo.order = 1;
+            rtg_frame* fr = nullptr;
+            rc = rtg_frame_create(gpu, &c.d, &o, &fo, &fr);
+            if (rc) { g_err = rtg_last_error(); break; }
+            const std::string name = output_name(c, out_dir);
+            const int total = c.d.num_samples;
+            rtg_frame_adapt ad{};
+            ad.rel_tol = (float)rel_tol;
+            ad.min_samples = min_samples;
+            int32_t active = rtg_frame_active_pixels(fr);
+            for (int done = 0; done < total && active > 0 && rc == RTG_OK;) {
+                const int n = step < total - done ? step : total - done;
+                rtg_frame_error er{};
+                if ((rc = rtg_frame_add_samples(fr, n, nullptr)) || (rc = rtg_frame_retire(fr, &ad, &active)) ||
+                    (rc = rtg_frame_resolve(fr, rgb.data())) || (rc = rtg_frame_error_stats(fr, &er))) {
+                    g_err = rtg_last_error();
+                    break;
+                }
+                done += n;
+                if ((rc = save_camera_images(c, name, rgb, device))) break;
+                printf("%s: %d/%d spp, mean_sem %.6g, mean_luminance %.6g, active %d\n", name.c_str(), done, total,
+                       er.mean_sem, er.mean_luminance, (int)active);
+                fflush(stdout);
+            }
+            rtg_frame_destroy(fr);
+            if (rc) break;
+        }
+        rtg_scene_destroy(gpu);
+        rtgh_free(sc);
+        return rc;
+    });
+}
+
 }  // extern "C"

@@ -174,7 +174,11 @@ TMO_PHOTOGRAPHIC = 0
 
 class FrameOpts(C.Structure):
     _fields_ = [("first_sample", C.c_int32), ("sample_count", C.c_int32), ("moments", C.c_int32),
-                ("pad", C.c_int32)]
+                ("order", C.c_int32)]
+
+
+class FrameAdapt(C.Structure):
+    _fields_ = [("rel_tol", C.c_float), ("abs_tol", C.c_float), ("min_samples", C.c_int32), ("pad", C.c_int32)]
 
 
 class FrameError(C.Structure):
@@ -229,6 +233,13 @@ EXPORTS = {
     "rtg_frame_get_state": (C.c_int32, [C.c_void_p, PF, PF]),
     "rtg_frame_set_state": (C.c_int32, [C.c_void_p, C.c_int32, PF, PF]),
     "rtg_frame_destroy": (C.c_int32, [C.c_void_p]),
+    # ABI 10 additions: sample order and per-pixel retirement (adaptive sampling)
+    "rtg_sample_order_index": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "rtg_frame_retire": (C.c_int32, [C.c_void_p, C.POINTER(FrameAdapt), PI]),
+    "rtg_frame_retire_mask": (C.c_int32, [C.c_void_p, C.c_void_p, PI]),
+    "rtg_frame_active_pixels": (C.c_int32, [C.c_void_p]),
+    "rtg_frame_sample_counts": (C.c_int32, [C.c_void_p, PI, C.c_void_p]),
+    "rtg_frame_set_retired": (C.c_int32, [C.c_void_p, PI, C.c_void_p]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

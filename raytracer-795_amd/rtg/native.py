@@ -44,6 +44,9 @@ def load():
         lib.rtgh_render_scene_progressive.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32,
                                                       C.c_double]
         lib.rtgh_render_scene_progressive.restype = C.c_int32
+        lib.rtgh_render_scene_adaptive.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32, C.c_double,
+                                                   C.c_int32]
+        lib.rtgh_render_scene_adaptive.restype = C.c_int32
         lib.rtgh_read_image.argtypes = [C.c_char_p, C.POINTER(A.PF), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.rtgh_read_image.restype = C.c_int32
         lib.rtgh_free_image.argtypes = [A.PF]
@@ -128,6 +131,15 @@ def render_scene_progressive(xml_path: str, step: int, target_error: float = 0.0
     lib = load()
     _check(lib.rtgh_render_scene_progressive(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None,
                                              int(step), float(target_error)))
+
+
+def render_scene_adaptive(xml_path: str, step: int, rel_tol: float, min_samples: int = 2, device: int = 0,
+                          seed: int = 0x5EED2026, out_dir: str | None = None):
+    """rtgh_render_scene_adaptive: rounds of `step` positions in sample order 1; after each round the pixels
+    whose standard error is at most rel_tol x their mean luminance are retired."""
+    lib = load()
+    _check(lib.rtgh_render_scene_adaptive(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None,
+                                          int(step), float(rel_tol), int(min_samples)))
 
 
 def _struct(s) -> dict:

@@ -44,12 +44,12 @@ class Renderer:
             self.handle = None
 
     def frame(self, camera: Camera | int = 0, first_sample: int = 0, sample_count: int = 0, moments: bool = False,
-              **kw) -> "Frame":
+              order: int = 0, **kw) -> "Frame":
         """A progressive frame of `camera` (rtg_frame): samples first_sample ..
         first_sample + sample_count - 1 of its num_samples (0 = through the last), added in chunks
-        with Frame.add; `kw` are the render options, fixed for the frame's life."""
+        with Frame.add; order 1 spreads every prefix over the pixel (§15); `kw`: the render options."""
         cam = self.scene.cameras[camera] if isinstance(camera, int) else camera
-        return Frame(self, cam, first_sample, sample_count, moments, self.opts(**kw))
+        return Frame(self, cam, first_sample, sample_count, moments, self.opts(**kw), order)
 
     def __del__(self):
         try:
@@ -329,14 +329,15 @@ class Frame:
             img = f.resolve()
     """
 
-    def __init__(self, renderer: Renderer, cam: Camera, first_sample: int, sample_count: int, moments: bool, opts):
+    def __init__(self, renderer: Renderer, cam: Camera, first_sample: int, sample_count: int, moments: bool, opts,
+                 order: int = 0):
         self.lib = renderer.lib
         self.renderer = renderer
         self.camera = cam
         self.opts = opts
         self.has_moments = bool(moments)
         self.handle = None
-        fo = A.FrameOpts(int(first_sample), int(sample_count), int(self.has_moments), 0)
+        fo = A.FrameOpts(int(first_sample), int(sample_count), int(self.has_moments), int(order))
         cd = cam.desc()
         h = C.c_void_p()
         A.check(self.lib.rtg_frame_create(renderer.handle, C.byref(cd), C.byref(opts), C.byref(fo), C.byref(h)),
@@ -400,7 +401,10 @@ class Frame:
         mom = np.zeros((self.rows, self.camera.nx, 2), np.float32) if self.has_moments else None
         A.check(self.lib.rtg_frame_get_state(self.handle, sums.ctypes.data_as(A.PF),
                                              None if mom is None else mom.ctypes.data_as(A.PF)), self.lib)
-        return {"samples_done": self.samples_done, "sums": sums, "moments": mom}
+        st = {"samples_done": self.samples_done, "sums": sums, "moments": mom}
+        if self.active < self.rows * self.camera.nx:
+            st["counts"], st["retired"] = self.counts()
+        return st
 
     def restore(self, state: dict):
         sums = np.ascontiguousarray(state["sums"], np.float32)
@@ -409,3 +413,39 @@ class Frame:
             raise ValueError("frame state of another size")
         A.check(self.lib.rtg_frame_set_state(self.handle, int(state["samples_done"]), sums.ctypes.data_as(A.PF),
                                              None if mom is None else mom.ctypes.data_as(A.PF)), self.lib)
+        if state.get("retired") is not None:
+            cnt = np.ascontiguousarray(state["counts"], np.int32)
+            ret = np.ascontiguousarray(state["retired"], np.uint8)
+            if cnt.size != self.rows * self.camera.nx or ret.size != cnt.size:
+                raise ValueError("frame state of another size")
+            A.check(self.lib.rtg_frame_set_retired(self.handle, cnt.ctypes.data_as(A.PI), ret.ctypes.data), self.lib)
+
+    # ---- adaptive sampling: retired pixels keep their samples and are traced no further
+    @property
+    def active(self) -> int:
+        """Owned pixels that add() still traces."""
+        return int(self.lib.rtg_frame_active_pixels(self.handle))
+
+    def retire(self, rel_tol: float = 0.0, abs_tol: float = 0.0, min_samples: int = 2) -> int:
+        """Retire every active pixel whose standard error is at most max(abs_tol, rel_tol * its mean
+        luminance), once samples_done >= max(min_samples, 2); returns the active pixels left."""
+        a = A.FrameAdapt(float(rel_tol), float(abs_tol), int(min_samples), 0)
+        n = C.c_int32()
+        A.check(self.lib.rtg_frame_retire(self.handle, C.byref(a), C.byref(n)), self.lib)
+        return n.value
+
+    def retire_mask(self, mask) -> int:
+        """Retire the active pixels where `mask` (owned-row shape) is set; returns the active pixels left."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if m.size != self.rows * self.camera.nx:
+            raise ValueError("mask of another size")
+        n = C.c_int32()
+        A.check(self.lib.rtg_frame_retire_mask(self.handle, m.ctypes.data, C.byref(n)), self.lib)
+        return n.value
+
+    def counts(self):
+        """(counts, retired): samples held per owned pixel (int32) and the retired flags (bool)."""
+        cnt = np.zeros((self.rows, self.camera.nx), np.int32)
+        ret = np.zeros((self.rows, self.camera.nx), np.uint8)
+        A.check(self.lib.rtg_frame_sample_counts(self.handle, cnt.ctypes.data_as(A.PI), ret.ctypes.data), self.lib)
+        return cnt, ret.astype(bool)
