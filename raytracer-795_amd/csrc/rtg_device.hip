@@ -2040,8 +2040,8 @@ DEV void shade_ray(const SceneView& sv, const CameraDev& cam, int level, const P
                     for (int li = 0; li < sv.num_lights; li++) {
                         ShadowRec sr;
                         light_sample<FULL, SPOT, (FULL && TEX) ? 2 : 0, false>(sv, li, d, time, ret, m, seed, pixel, sample, path, sr);
-                        // one light: a query that is not traced is never read (k_light_sum reads
-                        // every record when there are several)
+                        if (term_absorbed(sv.absorb_skip, sv.num_lights, nd.cr, nd.cg, nd.cb, sr.c)) sr.c.w = 0.0f;   // (rtg_internal.h)
+                        // one light: a query that is not traced is never read (k_light_sum reads every record when several)
                         if (sr.c.w != 0.0f || sv.num_lights > 1) {
                             const size_t k = (size_t)li * shadows.nn + i;     // light-major (ShadowPlanes)
                             if (sv.lean_shadow && !sv.has_blur) {

@@ -2296,7 +2296,7 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
     sv.num_gtris = s->num_gtris;
     sv.num_gents = s->num_gents;
     for (int z = 0; z < 3; z++) sv.tlas_k[z] = s->tlas_k[z];
-    sv.pt_flags = 0; sv.child_split = child_split_default();   // (RTG_CHILD_SPLIT, rtg_internal.h)
+    sv.pt_flags = 0; sv.child_split = child_split_default(); sv.absorb_skip = absorb_skip_default();   // (RTG_CHILD_SPLIT, RTG_ABSORB_SKIP, rtg_internal.h)
     sv.max_depth = d->max_recursion_depth;
     sv.shadow_eps = d->shadow_ray_eps;
     sv.int_eps = d->intersection_test_eps;
@@ -3834,6 +3834,12 @@ namespace rtg {
 // (SceneView::child_split, queue_slots in rtg_internal.h); anything else, or unset: the split.
 int child_split_default() {
     const char* e = getenv("RTG_CHILD_SPLIT");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+// RTG_ABSORB_SKIP=0: k_shade queues a single light's shadow query even where the ambient sum absorbs its
+// term (SceneView::absorb_skip, term_absorbed in rtg_internal.h); anything else, or unset: such queries are skipped.
+int absorb_skip_default() {
+    const char* e = getenv("RTG_ABSORB_SKIP");
     return !(e && e[0] == '0' && e[1] == 0);
 }
 }  // namespace rtg

@@ -181,7 +181,7 @@ struct SceneView {
     const float* texcoords;        // uv
     int num_texcoords;
     const MaterialDev* materials; int num_materials; int child_split;   // child_split: queue_slots (below; in former padding)
-    const TextureDev* textures; int num_textures;
+    const TextureDev* textures; int num_textures; int absorb_skip;   // absorb_skip: term_absorbed (below; in former padding)
     const float* texels;
     const LightDev* lights; int num_lights;
     int max_depth;
@@ -670,8 +670,20 @@ void device_warm(hipStream_t st);
 // SceneView::child_split as rtg_scene_create sets it (rtg_host.cpp): on unless RTG_CHILD_SPLIT=0 is in the
 // environment -- read per scene creation: a data switch for A/B runs and the tests, same device code.
 int child_split_default();
+// SceneView::absorb_skip likewise: on unless RTG_ABSORB_SKIP=0 is in the environment (term_absorbed, below).
+int absorb_skip_default();
 
 #ifdef __HIPCC__
+// One light: the query's node is fl(amb + c) if the light is visible and amb if it is blocked (amb: the
+// running sum, 0 + La*ka, never -0; c: the unshadowed term, c.w its mode).  Where fl(amb + c) has amb's bits in
+// every channel the query need not be traced; integer compares, so a NaN term keeps its query.  Not applied
+// with several lights.  `on`: SceneView::absorb_skip (RTG_ABSORB_SKIP=0 clears it).  DESIGN.md section 16.
+__device__ __forceinline__ bool term_absorbed(int on, int num_lights, float ar, float ag, float ab, const float4& c) {
+    if (!on || num_lights != 1 || !(c.w == 1.0f || c.w == 2.0f)) return false;
+    return ((__float_as_uint(ar + c.x) ^ __float_as_uint(ar)) | (__float_as_uint(ag + c.y) ^ __float_as_uint(ag)) |
+            (__float_as_uint(ab + c.z) ^ __float_as_uint(ab))) == 0u;
+}
+
 // k_shade's compaction of a level's child rays and shadow queries (shade_ray, rtg_device.hip; called by
 // every thread of a BLOCK-thread block): ballot prefixes inside each wave, wave totals combined in LDS,
 // one 64-bit atomic per block on the level's queue counter (low word: rays, high word: shadow entries).
