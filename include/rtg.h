@@ -608,6 +608,50 @@ int32_t rtg_frame_sample_counts(rtg_frame* frame, int32_t* counts_out, uint8_t* 
    counts[p] == samples_done for every pixel that is not retired. */
 int32_t rtg_frame_set_retired(rtg_frame* frame, const int32_t* counts, const uint8_t* retired);
 
+/* ---- ABI 10 additions: first-hit feature buffers and camera rays -------------
+   Additive: the version stays 10, no struct grows.
+
+   rtg_render_aov: per owned pixel, over a window of the camera's samples, what the primary rays hit
+   first -- the inputs of a denoiser, a compositor or an id picker.  Sample k of a pixel is the primary
+   ray rtg_render traces for it under opts->seed (a one-sample camera keeps its pixel-centre ray).  The
+   window's samples are visited in index order; for a sample that hits, t is the rtg_hit.t and n the
+   rtg_hit.normal (the shading normal: after bump / replace-normal textures and the object's transform)
+   that rtg_trace_closest reports for that ray, and a the diffuse reflectance its shading would use, by
+   the hit's decal mode: replace_kd / replace_all: tc / tn; blend_kd: (kd + tc / tn) * 0.5f; else kd
+   (kd: the material's diffuse, instance override applied; tc, tn: texture colour and normalizer;
+   component-wise float32).  depth, normal and albedo each start at +0, add t, n, a of the hit samples
+   in window order and divide by (float)hits; 0 where hits == 0.  normal is not renormalised.  ids
+   describe the window's FIRST sample alone: (top-level object, primitive in parse order as
+   rtg_hit.prim, 1-based material), or (-1, -1, 0) for a miss.
+   Layout and ownership are rtg_render's: [y][x][c], rows the shard does not own written as 0 (ids:
+   -1, -1, 0); with compact_rows only the owned rows.  seed, row_offset, row_stride, row_block,
+   compact_rows and traversal are honoured; the other option fields, the camera's integrator and its
+   pt_flags do not change the result.  num_devices > 1 or devices != NULL: RTG_ERR_UNSUPPORTED.
+   rtg_last_render_stats then reports primary_rays = total_rays = owned pixels x window and the device
+   time in render_ms.  The call may interleave with renders and frames on the scene (never run
+   concurrently with them) and leaves a live frame's accumulator untouched.  opts / aov may be NULL
+   (seed 0, the whole camera). */
+typedef struct rtg_aov_opts {      /* 16 bytes */
+    int32_t first_sample;          /* window of the camera's num_samples, in index order */
+    int32_t sample_count;          /* 0 = through the last sample */
+    int32_t pad[2];                /* must be 0 */
+} rtg_aov_opts;
+typedef struct rtg_aov_buffers {   /* host pointers; each may be NULL, not all */
+    int32_t* hits;    /* 1 per pixel: samples of the window whose primary ray hit */
+    float*   depth;   /* 1 per pixel */
+    float*   normal;  /* 3 per pixel */
+    float*   albedo;  /* 3 per pixel */
+    int32_t* ids;     /* 3 per pixel: object, prim, material of the window's FIRST sample */
+} rtg_aov_buffers;
+int32_t rtg_render_aov(rtg_scene* scene, const rtg_camera_desc* cam, const rtg_render_opts* opts,
+                       const rtg_aov_opts* aov, const rtg_aov_buffers* out);
+/* The camera's primary rays for every pixel of the whole image (no sharding), as the renderer forms them
+   under `seed`: rays_out[(y * nx + x) * count + j] is sample first_sample + j (count = sample_count, or
+   num_samples - first_sample for 0): origin, direction and time (0 for a one-sample or depth-of-field
+   camera).  Computed on the scene's device.  Ready for rtg_trace_closest. */
+int32_t rtg_camera_rays(rtg_scene* scene, const rtg_camera_desc* cam, uint64_t seed, int32_t first_sample,
+                        int32_t sample_count, rtg_ray* rays_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,11 @@ extern int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t devic
    active pixel or its last sample.  (`extern` as above.) */
 extern int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
                                           int32_t step, double rel_tol, int32_t min_samples);
+/* rtgh_render_scene with the first-hit feature images (rtg_render_aov over each camera's full sample
+   range): beside a camera's image, three more through rtgh_save_image, named like it with
+   _normal, _albedo and _depth before the extension: (normal * 0.5f + 0.5f) * 255.0f, albedo * 255.0f and
+   the depth in all three channels.  (`extern` as above.) */
+extern int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir);
 
 #ifdef __cplusplus
 }

@@ -3522,4 +3522,167 @@ void launch_hit_details(const SceneView& sv, const RayQ rays, const HitRec* hits
     hipLaunchKernelGGL(k_hit_details, dim3(nblk(n, 256)), dim3(256), 0, st, sv, rays, hits, out, orig_prim, n);
 }
 
+// ------------------------------------------------------------------ first-hit feature buffers
+// k_aov: one lane per sample slot of the pass (pixels [ps.p0, ps.p0 + ps.npass) of the tiled pixel order x the
+// window [ps.s0, ps.s0 + ps.ns)), the layout of k_trace's generated rays: slot i is primary_ray(i) -- the ray
+// rtg_render traces for that pixel and sample -- walked by closest_hit with k_trace's stack set-up, a hit
+// rebuilt by hit_record.  A wave holds 64 samples of one pixel (or the samples of adjacent pixels), near-identical
+// rays that share the wave-uniform walk; one lane per pixel looping over its samples, a wave then an 8 x 8 tile
+// of pixels, measured 4 x slower on dragon1m at 64 spp.  Each slot leaves a 32-byte record
+// (a: t, normal; b: albedo, hit flag) and a window's first sample its pixel's ids; k_aov_reduce then sums a
+// pixel's records in sample order, one lane per pixel -- no atomics, the order is the loop's.
+// TEX = false: the scene has no textures (SceneView::tex), so hit_record's texturing is compiled out.
+#ifndef RTG_AOV_TEX_WAVES
+#define RTG_AOV_TEX_WAVES RTG_TRAVERSAL_WAVES
+#endif
+#define RTG_AOV_ATTR __attribute__((amdgpu_waves_per_eu(TLAS ? RTG_TLAS_WAVES : TEX ? RTG_AOV_TEX_WAVES : RTG_TRAVERSAL_WAVES)))
+template <bool EXHAUSTIVE, bool TLAS, bool TEX>
+__global__ void __launch_bounds__(kTraceBlock) RTG_AOV_ATTR k_aov(const SceneView sv, const CameraDev cam, const PassDev ps,
+                                                                    uint64_t seed, int n, const int* __restrict__ orig_prim,
+                                                                    float4* __restrict__ rec_a, float4* __restrict__ rec_b,
+                                                                    const AovPlanes out) {
+    __shared__ int s_stack[kLdsStack * kTraceBlock];
+    __shared__ short s_tstack[TLAS ? kTlasStack * kTraceBlock : 1];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    f3 o, d;
+    float time;
+    primary_ray(cam, ps, seed, i, o, d, time);
+    // camera samples only: the wave-uniform walk, as k_trace's generated rays
+    constexpr bool KUNI = !TLAS && !EXHAUSTIVE;
+    const bool uni = KUNI && sv.uni_walk;
+    const HitRec h = closest_hit<EXHAUSTIVE, false, TLAS, KUNI>(sv, o, d, time, FLT_MAX, s_stack + threadIdx.x, kTraceBlock,
+                                                                st, s_tstack + (TLAS ? threadIdx.x : 0), uni, nullptr);
+    float4 ra = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb = ra;
+    int id_obj = -1, id_prim = -1, id_mat = 0;
+    if (h.obj >= 0) {
+        const Ret ret = hit_record<TEX>(sv, o, d, time, h);
+        // the diffuse reflectance of diffuse_term
+        f3 a = ld3(sv.materials[ret.matIndex - 1].diffuse);
+        if (ret.dm == RTG_DECAL_REPLACE_KD || ret.dm == RTG_DECAL_REPLACE_ALL) a = ret.tc / ret.tn;
+        else if (ret.dm == RTG_DECAL_BLEND_KD) a = (a + ret.tc / ret.tn) * 0.5f;
+        ra = make_float4(h.t, ret.normal.x, ret.normal.y, ret.normal.z);
+        rb = make_float4(a.x, a.y, a.z, __int_as_float(1));
+        id_obj = h.obj; id_prim = orig_prim[h.prim]; id_mat = ret.matIndex;
+    }
+    rec_a[i] = ra;
+    rec_b[i] = rb;
+    const int pl = idiv(i, ps.ns);
+    if (i == pl * ps.ns) {          // the window's first sample
+        const size_t t = (size_t)ps.p0 + (size_t)pl, np = out.npix;
+        out.ids[t] = id_obj; out.ids[np + t] = id_prim; out.ids[2 * np + t] = id_mat;
+    }
+}
+
+// A pixel's records summed in sample order: one lane per pixel of the pass, planar stores in tile order.
+__global__ void __launch_bounds__(256) k_aov_reduce(const float4* __restrict__ rec_a, const float4* __restrict__ rec_b, int p0,
+                                                    int npass, int ns, const AovPlanes out) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npass) return;
+    const size_t base = (size_t)p * (size_t)ns;
+    int nh = 0;
+    float sd = 0.0f;
+    f3 sn = mk(0, 0, 0), sa = mk(0, 0, 0);
+    for (int j = 0; j < ns; j++) {
+        const float4 b = rec_b[base + j];
+        if (__float_as_int(b.w) == 0) continue;
+        const float4 a = rec_a[base + j];
+        nh++;
+        sd = sd + a.x;
+        sn = sn + mk(a.y, a.z, a.w);
+        sa = sa + mk(b.x, b.y, b.z);
+    }
+    if (nh > 0) {
+        const float fn = (float)nh;
+        sd = sd / fn; sn = sn / fn; sa = sa / fn;
+    }
+    const size_t t = (size_t)p0 + (size_t)p, np = out.npix;
+    out.hits[t] = nh;
+    out.depth[t] = sd;
+    out.normal[t] = sn.x; out.normal[np + t] = sn.y; out.normal[2 * np + t] = sn.z;
+    out.albedo[t] = sa.x; out.albedo[np + t] = sa.y; out.albedo[2 * np + t] = sa.z;
+}
+
+// Tile-order index of owned pixel (x, k): the inverse of tile_pixel.
+DEV size_t tile_index(int x, int k, int nx, int rows_owned, int th, int ts) {
+    const int tw = 64 >> __builtin_ctz((unsigned)th);
+    const int sh = th * ts;
+    const int band = idiv(k, sh), kk = k - band * sh;
+    const int hs = min(sh, rows_owned - sh * band);
+    const int c = idiv(x, tw);
+    const int wb = min(tw, nx - tw * c);
+    const int rt = idiv(kk, th), r = kk - rt * th;
+    return (size_t)band * sh * nx + (size_t)(c * tw) * hs + (size_t)(rt * wb * th + r * wb + (x - tw * c));
+}
+
+// The planes into rtg_render's layout: one lane per output pixel ([y][x][c]; rows the shard does not own read
+// 0 and ids (-1, -1, 0); compact: the owned rows only).
+__global__ void __launch_bounds__(256) k_aov_place(const AovPlanes in, const AovPlanes out, int nx, int out_rows, const PassDev ps,
+                                                   int compact) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)out_rows * nx) return;
+    const int y = (int)(e / (size_t)nx), x = (int)(e - (size_t)y * nx);
+    const int k = compact ? y : shard_owned_index(y, ps.row_offset, ps.row_stride, ps.row_block);
+    int nh = 0, i0 = -1, i1 = -1, i2 = 0;
+    float sd = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f, a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+    if (k >= 0) {
+        const size_t t = tile_index(x, k, nx, ps.rows_owned, ps.tile_h, ps.tile_s), np = in.npix;
+        nh = in.hits[t]; sd = in.depth[t];
+        n0 = in.normal[t]; n1 = in.normal[np + t]; n2 = in.normal[2 * np + t];
+        a0 = in.albedo[t]; a1 = in.albedo[np + t]; a2 = in.albedo[2 * np + t];
+        i0 = in.ids[t]; i1 = in.ids[np + t]; i2 = in.ids[2 * np + t];
+    }
+    out.hits[e] = nh;
+    out.depth[e] = sd;
+    out.normal[3 * e] = n0; out.normal[3 * e + 1] = n1; out.normal[3 * e + 2] = n2;
+    out.albedo[3 * e] = a0; out.albedo[3 * e + 1] = a1; out.albedo[3 * e + 2] = a2;
+    out.ids[3 * e] = i0; out.ids[3 * e + 1] = i1; out.ids[3 * e + 2] = i2;
+}
+
+// The camera's rays as primary_ray forms them: one lane per (pixel, sample) of the range; ps is a row-major
+// pass (tile_h = tile_s = 1 over all rows: tile order = image order), so slot i is pixel ps.p0 + i / ns in
+// image order and out[i] its sample ps.s0 + i % ns.
+__global__ void __launch_bounds__(256) k_camera_rays(const CameraDev cam, const PassDev ps, uint64_t seed, int n,
+                                                     rtg_ray* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 o, d;
+    float time;
+    primary_ray(cam, ps, seed, i, o, d, time);
+    rtg_ray r;
+    r.origin[0] = o.x; r.origin[1] = o.y; r.origin[2] = o.z;
+    r.direction[0] = d.x; r.direction[1] = d.y; r.direction[2] = d.z;
+    r.time = time;
+    out[i] = r;
+}
+
+void launch_aov(const SceneView& sv, const CameraDev& cam, const PassDev& ps, uint64_t seed, int exhaustive,
+                const int* orig_prim, float4* rec_a, float4* rec_b, const AovPlanes& out, hipStream_t st) {
+    const int n = ps.npass * ps.ns;            // the caller keeps a pass's slots within int
+    if (n <= 0) return;
+    dim3 g(nblk(n, kTraceBlock)), b(kTraceBlock);
+    const bool tl = sv.tlas_root >= 0;
+#define RTG_AOV(EX, TL)                                                                                              \
+    do {                                                                                                             \
+        if (sv.tex) hipLaunchKernelGGL((k_aov<EX, TL, true>), g, b, 0, st, sv, cam, ps, seed, n, orig_prim, rec_a, rec_b, out); \
+        else hipLaunchKernelGGL((k_aov<EX, TL, false>), g, b, 0, st, sv, cam, ps, seed, n, orig_prim, rec_a, rec_b, out); \
+    } while (0)
+    if (exhaustive) RTG_AOV(true, false);      // the literal object loop, as k_trace's exhaustive variant
+    else if (tl) RTG_AOV(false, true);
+    else RTG_AOV(false, false);
+#undef RTG_AOV
+    hipLaunchKernelGGL(k_aov_reduce, dim3(nblk(ps.npass, 256)), dim3(256), 0, st, rec_a, rec_b, ps.p0, ps.npass, ps.ns, out);
+}
+void launch_aov_place(const AovPlanes& in, const AovPlanes& out, int nx, int out_rows, const PassDev& ps, int compact,
+                      hipStream_t st) {
+    const size_t n = (size_t)out_rows * nx;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_aov_place, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, nx, out_rows, ps, compact);
+}
+void launch_camera_rays(const CameraDev& cam, const PassDev& ps, uint64_t seed, int n, rtg_ray* out, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_camera_rays, dim3(nblk(n, 256)), dim3(256), 0, st, cam, ps, seed, n, out);
+}
+
 }  // namespace rtg

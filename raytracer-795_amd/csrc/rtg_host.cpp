@@ -3827,6 +3827,145 @@ int32_t rtg_scene_vertex_normals(const rtg_scene* s, float* normals) {
     return RTG_OK;
 }
 
+// ---------------------------------------------------------------- first-hit feature buffers
+// A sample window against the camera: count 0 = through the last sample (rtg_frame_create's rule).
+static int aov_window(const rtg_camera_desc* cam, int first, int count, int& window) {
+    if (cam->nx < 1 || cam->ny < 1 || cam->num_samples < 1) return fail(RTG_ERR_INVALID, "bad camera");
+    if (first < 0 || first >= cam->num_samples || count < 0 || count > cam->num_samples - first)
+        return fail(RTG_ERR_INVALID, "sample window outside the camera's samples");
+    window = count > 0 ? count : cam->num_samples - first;
+    return RTG_OK;
+}
+
+int32_t rtg_render_aov(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, const rtg_aov_opts* aopts,
+                       const rtg_aov_buffers* out) {
+    return guarded([&]() -> int32_t {
+        if (!s || !cam || !out) return fail(RTG_ERR_INVALID, "null argument");
+        if (!out->hits && !out->depth && !out->normal && !out->albedo && !out->ids)
+            return fail(RTG_ERR_INVALID, "no output buffer");
+        rtg_aov_opts ao{};
+        if (aopts) ao = *aopts;
+        if (ao.pad[0] || ao.pad[1]) return fail(RTG_ERR_INVALID, "rtg_aov_opts.pad must be 0");
+        int window = 0, rc;
+        if ((rc = aov_window(cam, ao.first_sample, ao.sample_count, window))) return rc;
+        rtg_render_opts o{};
+        if (opts) o = *opts;
+        if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_UNSUPPORTED, "feature buffers render on the scene's device only");
+        const int stride = o.row_stride > 1 ? o.row_stride : 1, block = o.row_block > 1 ? o.row_block : 1;
+        if (o.row_offset < 0 || o.row_offset >= stride) return fail(RTG_ERR_INVALID, "row_offset out of range");
+        const int rows_owned = rtg_shard_rows(cam->ny, o.row_offset, stride, block);
+        if ((long long)rows_owned * cam->nx > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
+        if ((long long)8 * cam->nx >= (1LL << 31)) return fail(RTG_ERR_UNSUPPORTED, "image wider than 2^28 pixels");
+        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+        HIP_TRY(hipSetDevice(s->device));
+        const int npix = rows_owned * cam->nx;
+        const int out_rows = o.compact_rows ? rows_owned : cam->ny;
+        const size_t nout = (size_t)out_rows * cam->nx;
+        // render_impl's pixel order with the default band height
+        PassDev ps{};
+        ps.s0 = ao.first_sample; ps.ns = window;
+        ps.row_offset = o.row_offset; ps.row_stride = stride; ps.rows_owned = rows_owned; ps.row_block = block;
+        ps.tile_h = stride > 1 && block < 8 ? (block >= 4 ? 4 : block >= 2 ? 2 : 1) : 8;
+        ps.tile_s = (int)std::min<long long>(std::max(1, kBandRows / ps.tile_h), ((1LL << 31) - 1) / (8LL * cam->nx));
+        const CameraDev cd = make_camera(cam);
+
+        struct Scratch {                    // RAII: released on every return path
+            DBuf rec, tile, img;
+            hipEvent_t e[2] = {};
+            ~Scratch() { rec.release(); tile.release(); img.release(); for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+        } w;
+        // 11 words per pixel: hits 1, depth 1, normal 3, albedo 3, ids 3
+        if ((rc = w.tile.grow(44 * std::max<size_t>(npix, 1))) || (rc = w.img.grow(44 * std::max<size_t>(nout, 1)))) return rc;
+        auto planes = [](void* base, size_t n) {
+            int* p = static_cast<int*>(base);
+            return AovPlanes{p, reinterpret_cast<float*>(p + n), reinterpret_cast<float*>(p + 2 * n),
+                             reinterpret_cast<float*>(p + 5 * n), p + 8 * n, n};
+        };
+        const AovPlanes tp = planes(w.tile.p, (size_t)npix), ip = planes(w.img.p, nout);
+        // passes: pixel ranges of whole tiles with at most 4M sample slots (128 MB of records) -- a longer
+        // window takes one pixel per pass (its slots stay within int: make_camera's sample grid ends at 10^6
+        // samples) -- dealt round-robin to up to four of the scene's lanes, each with its own records, so one
+        // pass's reduction (few, long lanes) runs beside the next passes' traversal; the passes write
+        // disjoint pixel ranges of the planes, and the null stream joins the lanes before the placement
+        const long long kSlots = 4LL << 20;
+        const int chunk = window >= kSlots ? 1 : (int)std::max<long long>(1, kSlots / window >= 64 ? (kSlots / window) & ~63LL : kSlots / window);
+        if ((long long)window * chunk > (1LL << 31) - 1) return fail(RTG_ERR_UNSUPPORTED, "sample window too long");
+        const int npasses = (npix + chunk - 1) / chunk;
+        const int L = std::max(1, std::min(4, npasses));
+        while ((int)s->lanes.size() < L) {
+            s->lanes.emplace_back();
+            if ((rc = s->lanes.back().create())) { s->lanes.back().destroy(); s->lanes.pop_back(); return rc; }
+        }
+        const size_t slots = (size_t)std::min(chunk, std::max(npix, 1)) * window;
+        if ((rc = w.rec.grow(kAovRecBytes * slots * L))) return rc;
+        for (hipEvent_t& x : w.e) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(w.e[0], nullptr));
+        for (int k = 0; k < L; k++) HIP_TRY(hipStreamWaitEvent(s->lanes[k].st, w.e[0], 0));
+        int launches = 0;
+        for (int p0 = 0; p0 < npix; p0 += chunk, launches++) {
+            const int k = launches % L;
+            float4* rec_a = w.rec.as<float4>() + (size_t)2 * slots * k;
+            ps.p0 = p0; ps.npass = std::min(chunk, npix - p0);
+            launch_aov(s->sv, cd, ps, o.seed, o.traversal == 1, s->d_origprim.as<int>(), rec_a, rec_a + slots, tp, s->lanes[k].st);
+        }
+        for (int k = 0; k < L; k++) {
+            HIP_TRY(hipEventRecord(s->lanes[k].ev_join, s->lanes[k].st));
+            HIP_TRY(hipStreamWaitEvent(nullptr, s->lanes[k].ev_join, 0));
+        }
+        launch_aov_place(tp, ip, cam->nx, out_rows, ps, o.compact_rows != 0, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(w.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(w.e[1]));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, w.e[0], w.e[1]));
+        if (nout) {
+            if (out->hits) HIP_TRY(hipMemcpy(out->hits, ip.hits, 4 * nout, hipMemcpyDeviceToHost));
+            if (out->depth) HIP_TRY(hipMemcpy(out->depth, ip.depth, 4 * nout, hipMemcpyDeviceToHost));
+            if (out->normal) HIP_TRY(hipMemcpy(out->normal, ip.normal, 12 * nout, hipMemcpyDeviceToHost));
+            if (out->albedo) HIP_TRY(hipMemcpy(out->albedo, ip.albedo, 12 * nout, hipMemcpyDeviceToHost));
+            if (out->ids) HIP_TRY(hipMemcpy(out->ids, ip.ids, 12 * nout, hipMemcpyDeviceToHost));
+        }
+        rtg_render_stats st{};
+        st.primary_rays = st.total_rays = (uint64_t)npix * (uint64_t)window;
+        st.render_ms = ms;
+        st.passes = launches;
+        st.devices = 1;
+        s->stats = st;
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_camera_rays(rtg_scene* s, const rtg_camera_desc* cam, uint64_t seed, int32_t first_sample, int32_t sample_count,
+                        rtg_ray* rays_out) {
+    return guarded([&]() -> int32_t {
+        if (!s || !cam || !rays_out) return fail(RTG_ERR_INVALID, "null argument");
+        int window = 0, rc;
+        if ((rc = aov_window(cam, first_sample, sample_count, window))) return rc;
+        if ((long long)cam->nx * cam->ny > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
+        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot form rays");
+        HIP_TRY(hipSetDevice(s->device));
+        const int npix = cam->nx * cam->ny;
+        // a row-major pass: one-row tiles in one-tile bands over every row make tile order image order
+        PassDev ps{};
+        ps.s0 = first_sample; ps.ns = window;
+        ps.row_offset = 0; ps.row_stride = 1; ps.rows_owned = cam->ny; ps.row_block = 1;
+        ps.tile_h = 1; ps.tile_s = 1;
+        const CameraDev cd = make_camera(cam);
+        // pixel ranges of at most 4M rays (one pixel's window if that is longer): a bounded staging buffer
+        const int chunk = (int)std::max<long long>(1, (4LL << 20) / window);
+        struct Scratch { DBuf d; ~Scratch() { d.release(); } } w;
+        if ((rc = w.d.grow(sizeof(rtg_ray) * (size_t)std::min(chunk, npix) * window))) return rc;
+        for (int p0 = 0; p0 < npix; p0 += chunk) {
+            ps.p0 = p0; ps.npass = std::min(chunk, npix - p0);
+            const size_t n = (size_t)ps.npass * window;
+            launch_camera_rays(cd, ps, seed, (int)n, w.d.as<rtg_ray>(), nullptr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(rays_out + (size_t)p0 * window, w.d.p, sizeof(rtg_ray) * n, hipMemcpyDeviceToHost));
+        }
+        return RTG_OK;
+    });
+}
+
 }  // extern "C"
 
 namespace rtg {

@@ -552,6 +552,28 @@ void launch_active_list(const unsigned* cnt, int npix, const PassDev& ps, int nx
                         hipStream_t st);
 void launch_hit_details(const SceneView& sv, const RayQ rays, const HitRec* hits, struct ::rtg_hit* out,
                         const int* orig_prim, int n, hipStream_t st);
+// First-hit feature buffers (rtg_render_aov).  A pass's samples leave 32-byte records (rec_a:
+// t, normal; rec_b: albedo, hit flag; one per slot, kAovRecBytes); k_aov_reduce sums a pixel's records in sample
+// order into planes over the npix owned pixels in tile order (hits / depth [t]; normal / albedo / ids
+// [c * npix + t]); k_aov_place turns them into the image layout ([e] and [3 * e + c] over the output's pixels,
+// npix unused).
+struct AovPlanes {
+    int* hits;
+    float* depth;
+    float* normal;
+    float* albedo;
+    int* ids;
+    size_t npix;
+};
+constexpr size_t kAovRecBytes = 32;
+// ps: the pixel range [p0, p0 + npass) x the window [s0, s0 + ns), npass * ns < 2^31; rec_a / rec_b: npass * ns each
+void launch_aov(const SceneView& sv, const CameraDev& cam, const PassDev& ps, uint64_t seed, int exhaustive,
+                const int* orig_prim, float4* rec_a, float4* rec_b, const AovPlanes& out, hipStream_t st);
+void launch_aov_place(const AovPlanes& in, const AovPlanes& out, int nx, int out_rows, const PassDev& ps, int compact,
+                      hipStream_t st);
+// rtg_camera_rays: ps is row-major (tile_h = tile_s = 1, no shard); out[i] = the ray of slot i, i < n
+void launch_camera_rays(const CameraDev& cam, const PassDev& ps, uint64_t seed, int n, struct ::rtg_ray* out,
+                        hipStream_t st);
 
 // Traversal-tree build records (rtg_host.cpp sah_split, rtg_sah_gpu.hip): one triangle's box and face
 // index (32 B; the centroid is the box centre), and the binned-SAH BVH2 node over a range of them.

@@ -21,6 +21,12 @@
 // --adaptive REL (with --progressive) samples adaptively: after each round the pixels whose standard error is
 // at most REL x their mean luminance (and that hold at least M samples, default 2) are retired and traced no
 // further; the round's line also reports the active pixels, and a camera ends with its last active pixel.
+//
+//   rtg_cli scene.xml --aov [--device N] [--seed S] [--out-dir DIR]
+//
+// --aov also writes every camera's first-hit feature images over its full sample range (rtg_render_aov):
+// the shading normal as (n * 0.5 + 0.5) * 255, the albedo * 255 and the depth, named like the camera's image
+// with _normal, _albedo and _depth before the extension.  One GPU, not with --progressive.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -33,7 +39,7 @@ int main(int argc, char** argv) {
     int device = 0, devices = 0, progressive = 0;
     bool have_progressive = false, have_target = false;
     double target_error = 0.0, adaptive = 0.0;
-    bool have_adaptive = false, have_min = false;
+    bool have_adaptive = false, have_min = false, aov = false;
     int min_samples = 2;
     unsigned long long seed = 0x5EED2026ull;
     for (int i = 1; i < argc; i++) {
@@ -45,16 +51,21 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--target-error") && i + 1 < argc) { target_error = atof(argv[++i]); have_target = true; }
         else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive = atof(argv[++i]); have_adaptive = true; }
         else if (!strcmp(argv[i], "--min-samples") && i + 1 < argc) { min_samples = atoi(argv[++i]); have_min = true; }
+        else if (!strcmp(argv[i], "--aov")) aov = true;
         else if (argv[i][0] == '-') { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         else xml = argv[i];
     }
     if (!xml) {
         fprintf(stderr, "usage: %s scene.xml [--device N] [--devices G] [--seed S] [--out-dir DIR] "
-                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]]]\n", argv[0]);
+                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]]] [--aov]\n", argv[0]);
         return 2;
     }
     if (have_progressive && devices > 0) {
         fprintf(stderr, "rtg_cli: --progressive renders on one GPU: it cannot be combined with --devices\n");
+        return 2;
+    }
+    if (aov && (have_progressive || devices > 0)) {
+        fprintf(stderr, "rtg_cli: --aov renders on one GPU in one go: it cannot be combined with --devices or --progressive\n");
         return 2;
     }
     if ((have_progressive && progressive < 1) || (have_target && (!have_progressive || !(target_error >= 0.0)))) {
@@ -69,6 +80,7 @@ int main(int argc, char** argv) {
     }
     const int rc = have_adaptive ? rtgh_render_scene_adaptive(xml, device, seed, out_dir, progressive, adaptive, min_samples)
                  : have_progressive ? rtgh_render_scene_progressive(xml, device, seed, out_dir, progressive, target_error)
+                 : aov              ? rtgh_render_scene_aov(xml, device, seed, out_dir)
                                     : rtgh_render_scene_multi(xml, device, devices, seed, out_dir);
     if (rc != RTG_OK) {
         fprintf(stderr, "rtg_cli: %s\n", rtgh_last_error());

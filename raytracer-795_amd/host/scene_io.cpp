@@ -1274,4 +1274,57 @@ int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, uint64_
     });
 }
 
+// A feature image's name: `suffix` before the extension of the camera's image name (a dot that starts the
+// file name is no extension).
+static std::string aov_name(const std::string& name, const char* suffix) {
+    const size_t sl = name.rfind('/'), base = sl == std::string::npos ? 0 : sl + 1;
+    size_t dot = name.rfind('.');
+    if (dot != std::string::npos && (dot < base || name.find_first_not_of('.', base) > dot)) dot = std::string::npos;
+    return dot == std::string::npos ? name + suffix : name.substr(0, dot) + suffix + name.substr(dot);
+}
+
+// rtgh_render_scene's camera loop with the first-hit feature images (rtg_render_aov).
+int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
+    return guarded([&]() -> int32_t {
+        rtgh_scene* sc = nullptr;
+        int rc = rtgh_parse_xml(xml_path, &sc);
+        if (rc) return rc;
+        rtg_scene* gpu = nullptr;
+        rtg_build_opts bo{};
+        bo.bvh_builder = RTG_BVH_AUTO;
+        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
+        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
+        printf("BVH construction complete.\n");
+        for (const CamData& c : sc->cameras) {
+            const size_t np = (size_t)c.d.nx * c.d.ny;
+            std::vector<float> rgb(np * 3), normal(np * 3), albedo(np * 3), depth(np), img(np * 3);
+            rtg_render_opts o{};
+            o.seed = seed;
+            rc = rtg_render(gpu, &c.d, &o, rgb.data());
+            if (rc) { g_err = rtg_last_error(); break; }
+            const std::string name = output_name(c, out_dir);
+            if ((rc = save_camera_images(c, name, rgb, device))) break;
+            rtg_render_stats st{};
+            rtg_last_render_stats(gpu, &st);
+            rtg_aov_buffers ab{};
+            ab.depth = depth.data(); ab.normal = normal.data(); ab.albedo = albedo.data();
+            rc = rtg_render_aov(gpu, &c.d, &o, nullptr, &ab);
+            if (rc) { g_err = rtg_last_error(); break; }
+            for (size_t i = 0; i < np * 3; i++) img[i] = (normal[i] * 0.5f + 0.5f) * 255.0f;
+            if ((rc = rtgh_save_image(aov_name(name, "_normal").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+            for (size_t i = 0; i < np * 3; i++) img[i] = albedo[i] * 255.0f;
+            if ((rc = rtgh_save_image(aov_name(name, "_albedo").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+            for (size_t i = 0; i < np * 3; i++) img[i] = depth[i / 3];
+            if ((rc = rtgh_save_image(aov_name(name, "_depth").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+            rtg_render_stats sa{};
+            rtg_last_render_stats(gpu, &sa);
+            printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s; feature buffers %.1f ms\n", name.c_str(), st.render_ms,
+                   st.total_rays / (st.render_ms * 1e3), st.devices, st.devices == 1 ? "" : "s", sa.render_ms);
+        }
+        rtg_scene_destroy(gpu);
+        rtgh_free(sc);
+        return rc;
+    });
+}
+
 }  // extern "C"

@@ -186,6 +186,14 @@ class FrameError(C.Structure):
                 ("samples_done", C.c_int32), ("pixels", C.c_int32)]
 
 
+class AovOpts(C.Structure):
+    _fields_ = [("first_sample", C.c_int32), ("sample_count", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class AovBuffers(C.Structure):
+    _fields_ = [("hits", PI), ("depth", PF), ("normal", PF), ("albedo", PF), ("ids", PI)]
+
+
 class Hit(C.Structure):
     _fields_ = [("full", C.c_int32), ("object", C.c_int32), ("prim", C.c_int32), ("material", C.c_int32),
                 ("t", C.c_float), ("point", F3), ("normal", F3)]
@@ -240,6 +248,11 @@ EXPORTS = {
     "rtg_frame_active_pixels": (C.c_int32, [C.c_void_p]),
     "rtg_frame_sample_counts": (C.c_int32, [C.c_void_p, PI, C.c_void_p]),
     "rtg_frame_set_retired": (C.c_int32, [C.c_void_p, PI, C.c_void_p]),
+    # ABI 10 additions: first-hit feature buffers and camera rays
+    "rtg_render_aov": (C.c_int32, [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderOpts), C.POINTER(AovOpts),
+                                   C.POINTER(AovBuffers)]),
+    "rtg_camera_rays": (C.c_int32, [C.c_void_p, C.POINTER(CameraDesc), C.c_uint64, C.c_int32, C.c_int32,
+                                    C.POINTER(Ray)]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

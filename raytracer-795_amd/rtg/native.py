@@ -47,6 +47,8 @@ def load():
         lib.rtgh_render_scene_adaptive.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32, C.c_double,
                                                    C.c_int32]
         lib.rtgh_render_scene_adaptive.restype = C.c_int32
+        lib.rtgh_render_scene_aov.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p]
+        lib.rtgh_render_scene_aov.restype = C.c_int32
         lib.rtgh_read_image.argtypes = [C.c_char_p, C.POINTER(A.PF), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.rtgh_read_image.restype = C.c_int32
         lib.rtgh_free_image.argtypes = [A.PF]
@@ -140,6 +142,12 @@ def render_scene_adaptive(xml_path: str, step: int, rel_tol: float, min_samples:
     lib = load()
     _check(lib.rtgh_render_scene_adaptive(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None,
                                           int(step), float(rel_tol), int(min_samples)))
+
+
+def render_scene_aov(xml_path: str, device: int = 0, seed: int = 0x5EED2026, out_dir: str | None = None):
+    """rtgh_render_scene_aov: every camera's image and its _normal / _albedo / _depth feature images."""
+    lib = load()
+    _check(lib.rtgh_render_scene_aov(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None))
 
 
 def _struct(s) -> dict:

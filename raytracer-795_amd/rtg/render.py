@@ -290,7 +290,7 @@ class Comm:
             pass
 
 
-def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed: int = DEFAULT_SEED) -> list:
+def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed: int = DEFAULT_SEED, aov: bool = False) -> list:
     """Scene::renderScene (src/Scene.cpp:294-363): every camera rendered and saved.  A camera
     with a hw5 <Tonemap> also gets its tone-mapped image (tonemapped_name; a .png ImageName is
     written tone-mapped instead of clamped)."""
@@ -305,7 +305,24 @@ def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed
                 written.append(save_image(name, img))
             if tm is not None:
                 written.append(save_image(tonemapped_name(name), tm))
+            if aov:      # rtg_cli --aov: the feature images over the camera's full sample range
+                for suffix, data in aov_images(r.aov(cam, seed=seed)):
+                    written.append(save_image(aov_name(name, suffix), data))
     return written
+
+
+def aov_name(name: str, suffix: str) -> str:
+    """Where a camera's feature image goes: `suffix` before its ImageName's extension."""
+    stem, ext = os.path.splitext(name)
+    return stem + suffix + ext
+
+
+def aov_images(a: dict) -> list:
+    """The feature images rtg_cli --aov writes, as (suffix, (ny, nx, 3) float32): the normal as
+    (n * 0.5 + 0.5) * 255, the albedo * 255 and the depth in all three channels."""
+    half, full = np.float32(0.5), np.float32(255.0)
+    return [("_normal", (a["normal"] * half + half) * full), ("_albedo", a["albedo"] * full),
+            ("_depth", np.repeat(a["depth"][:, :, None], 3, axis=2))]
 
 
 def _bvh(fn, handle, obj):
@@ -449,3 +466,50 @@ class Frame:
         ret = np.zeros((self.rows, self.camera.nx), np.uint8)
         A.check(self.lib.rtg_frame_sample_counts(self.handle, cnt.ctypes.data_as(A.PI), ret.ctypes.data), self.lib)
         return cnt, ret.astype(bool)
+
+
+# ---------------------------------------------------------------------------- feature buffers
+def _renderer_aov(self, camera: Camera | int = 0, first_sample: int = 0, sample_count: int = 0, **kw) -> dict:
+    """First-hit feature buffers of `camera` over samples first_sample .. first_sample + sample_count - 1
+    (0 = through the last) of its primary rays (rtg_render_aov): `hits` (ny, nx) int32, the samples that
+    hit; `depth` (ny, nx), `normal` and `albedo` (ny, nx, 3) float32, their in-order means over the hit
+    samples; `object`, `prim`, `material` (ny, nx) int32 of the window's first sample (-1, -1, 0 for a
+    miss).  `kw`: the render options (seed, row shards, compact_rows, traversal); layout as render()."""
+    cam = self.scene.cameras[camera] if isinstance(camera, int) else camera
+    o = self.opts(**kw)
+    rows = (self.lib.rtg_shard_rows(cam.ny, o.row_offset, o.row_stride, o.row_block) if o.compact_rows
+            else cam.ny)
+    hits = np.empty((rows, cam.nx), np.int32)
+    depth = np.empty((rows, cam.nx), np.float32)
+    normal = np.empty((rows, cam.nx, 3), np.float32)
+    albedo = np.empty((rows, cam.nx, 3), np.float32)
+    ids = np.empty((rows, cam.nx, 3), np.int32)
+    ao = A.AovOpts(int(first_sample), int(sample_count))
+    bufs = A.AovBuffers(hits.ctypes.data_as(A.PI), depth.ctypes.data_as(A.PF), normal.ctypes.data_as(A.PF),
+                        albedo.ctypes.data_as(A.PF), ids.ctypes.data_as(A.PI))
+    cd = cam.desc()
+    A.check(self.lib.rtg_render_aov(self.handle, C.byref(cd), C.byref(o), C.byref(ao), C.byref(bufs)), self.lib)
+    return {"hits": hits, "depth": depth, "normal": normal, "albedo": albedo,
+            "object": ids[:, :, 0].copy(), "prim": ids[:, :, 1].copy(), "material": ids[:, :, 2].copy()}
+
+
+def _renderer_camera_rays(self, camera: Camera | int = 0, first_sample: int = 0, sample_count: int = 0,
+                          seed: int = DEFAULT_SEED):
+    """(origins, directions, times) of the camera's primary rays as the renderer forms them under `seed`
+    (rtg_camera_rays): (ny, nx, count, 3) and (ny, nx, count) float32, sample first_sample + j at [y, x, j];
+    reshaped to (-1, 3) / (-1) they are ready for Renderer.trace and the oracle's trace."""
+    cam = self.scene.cameras[camera] if isinstance(camera, int) else camera
+    count = int(sample_count) if sample_count > 0 else max(cam.num_samples - int(first_sample), 0)
+    n = cam.ny * cam.nx * count
+    rays = (A.Ray * max(n, 1))()
+    cd = cam.desc()
+    A.check(self.lib.rtg_camera_rays(self.handle, C.byref(cd), int(seed), int(first_sample), int(sample_count), rays),
+            self.lib)
+    buf = np.frombuffer(rays, dtype=np.float32, count=7 * max(n, 1)).reshape(-1, 7)[:n]
+    shape = (cam.ny, cam.nx, count)
+    return (buf[:, 0:3].reshape(*shape, 3).copy(), buf[:, 3:6].reshape(*shape, 3).copy(), buf[:, 6].reshape(shape).copy())
+
+
+# (methods of Renderer, defined here so that the lines above them stay where they are)
+Renderer.aov = _renderer_aov
+Renderer.camera_rays = _renderer_camera_rays

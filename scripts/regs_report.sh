@@ -15,7 +15,7 @@ for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.vgpr_count:\s+(\d+)', s, re.S):
 # amdhsa metadata blocks: one per kernel
 for blk in s.split('  - .agpr_count')[1:]:
     name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-    if not re.search(r'k_(trace|shadow|shade|pt_shade)', name):
+    if not re.search(r'k_(trace|shadow|shade|pt_shade|aov)', name):
         continue
     g = lambda k: (re.search(r'\.' + k + r':\s+(\d+)', blk) or [0, '?'])[1]
     dem = name.replace('_ZN3rtg', '')[:60]
