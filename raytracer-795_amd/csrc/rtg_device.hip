@@ -3199,14 +3199,20 @@ static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 
 // The launchers that hand a pass to the kernels are templates over the pass type: PassDev (rtg_render, plain
 // frames), or PassDevA (an adaptive frame), which falls back to PassDev when it is plain().
+// with_pass makes that choice, for every launcher: f(pass) runs with the type whose kernels the pass takes.
+template <class F>
+static void with_pass(const PassDevA& ps, F&& f) {
+    if (ps.plain()) f(static_cast<const PassDev&>(ps));
+    else f(ps);
+}
+// gen_cam non-null: the launch generates primary rays (either integrator), else the pass is not read
 template <class PS>
 static void launch_trace_t(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
-                           hipStream_t st, const CameraDev* gen_cam, const PS* gen_ps, uint64_t seed, bool compact,
+                           hipStream_t st, const CameraDev* gen_cam, const PS& ps, uint64_t seed, bool compact,
                            int nq, int gbase) {
     if (n <= 0) return;
     dim3 g(nblk(n, kTraceBlock)), b(kTraceBlock);
     const CameraDev cam = gen_cam ? *gen_cam : CameraDev{};
-    const PS ps = gen_ps ? *gen_ps : PS{};
     const bool tl = sv.tlas_root >= 0;
 #define RTG_TRACE(EX, STA, GEN)                                                                                   \
     do {                                                                                                          \
@@ -3226,41 +3232,37 @@ static void launch_trace_t(const SceneView& sv, const RayQ rays, HitRec* hits, i
     }
 #undef RTG_TRACE
 }
-void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
-                  hipStream_t st, const CameraDev* gen_cam, const PassDev* gen_ps, uint64_t seed, bool compact,
-                  int nq, int gbase) {
-    launch_trace_t<PassDev>(sv, rays, hits, n, exhaustive, ctr, st, gen_cam, gen_ps, seed, compact, nq, gbase);
+void launch_trace_queued(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, hipStream_t st) {
+    launch_trace_t(sv, rays, hits, n, exhaustive, nullptr, st, nullptr, PassDev{}, 0, /*compact=*/false, 0, 0);
 }
-void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, Counters* ctr,
-                  hipStream_t st, const CameraDev* gen_cam, const PassDevA* gen_ps, uint64_t seed, bool compact,
-                  int nq, int gbase) {
-    if (!gen_cam || !gen_ps || gen_ps->plain())
-        launch_trace_t<PassDev>(sv, rays, hits, n, exhaustive, ctr, st, gen_cam, gen_ps, seed, compact, nq, gbase);
+void launch_trace(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+                  int exhaustive, Counters* ctr, hipStream_t st) {
+    if (!io.gen)
+        launch_trace_t(sv, io.rays, io.hits, io.n, exhaustive, ctr, st, nullptr, PassDev{}, seed, /*compact=*/true, io.nq, io.gbase);
     else
-        launch_trace_t<PassDevA>(sv, rays, hits, n, exhaustive, ctr, st, gen_cam, gen_ps, seed, compact, nq, gbase);
+        with_pass(ps, [&](const auto& p) {
+            launch_trace_t(sv, io.rays, io.hits, io.n, exhaustive, ctr, st, &cam, p, seed, /*compact=*/true, io.nq, io.gbase);
+        });
 }
 __global__ void k_warm() {}
 void device_warm(hipStream_t st) { hipLaunchKernelGGL(k_warm, dim3(1), dim3(64), 0, st); }
 
 template <class PS>
-static void launch_shade_t(const SceneView& sv, const CameraDev& cam, int level, const PS& ps, uint64_t seed,
-                           const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
-                           ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
-                           unsigned long long* qcount, int n, hipStream_t st,
-                           int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
+static void launch_shade_t(const SceneView& sv, const CameraDev& cam, const PS& ps, uint64_t seed, const StepIO& io,
+                           hipStream_t st) {
+    const int n = io.n;
     if (n <= 0) return;
     dim3 g(nblk(n, kShadeBlock)), b(kShadeBlock);
-    const NodePlanes np = node_planes(nodes, n);
-    const ShadowPlanes sp = shadow_planes(shadows, n, sv.num_lights);
-    const bool G = gen < 0 ? rays.a == nullptr : gen != 0;   // gen < 0: a pass's level (level 0 has no queue)
+    const NodePlanes np = node_planes(io.nodes, n);
+    const ShadowPlanes sp = shadow_planes(io.shadows, n, sv.num_lights);
 #define RTG_SHADE(F, S, B, T, gr, bl)                                                                             \
     do {                                                                                                          \
-        if (G)                                                                                                    \
-            hipLaunchKernelGGL((k_shade<F, S, B, T, true, PS>), gr, bl, 0, st, sv, cam, level, ps, seed, rays, meta, hits, np, sp, \
-                               slist, next_rays, next_meta, qcount, n, nq, gbase, lv_in, lv_out); \
+        if (io.gen)                                                                                               \
+            hipLaunchKernelGGL((k_shade<F, S, B, T, true, PS>), gr, bl, 0, st, sv, cam, io.level, ps, seed, io.rays, io.meta, io.hits, np, sp, \
+                               io.slist, io.next_rays, io.next_meta, io.qcount, n, io.nq, io.gbase, io.lv_in, io.lv_out); \
         else                                                                                                      \
-            hipLaunchKernelGGL((k_shade<F, S, B, T, false, PS>), gr, bl, 0, st, sv, cam, level, ps, seed, rays, meta, hits, np, sp, \
-                               slist, next_rays, next_meta, qcount, n, nq, gbase, lv_in, lv_out); \
+            hipLaunchKernelGGL((k_shade<F, S, B, T, false, PS>), gr, bl, 0, st, sv, cam, io.level, ps, seed, io.rays, io.meta, io.hits, np, sp, \
+                               io.slist, io.next_rays, io.next_meta, io.qcount, n, io.nq, io.gbase, io.lv_in, io.lv_out); \
     } while (0)
     // full variants: SPOT = a spot or environment light (their libm code compiled in)
     if (sv.full && sv.tex && sv.heavy) RTG_SHADE(true, true, 256, true, dim3(nblk(n, 256)), dim3(256));
@@ -3272,79 +3274,67 @@ static void launch_shade_t(const SceneView& sv, const CameraDev& cam, int level,
     else RTG_SHADE(false, false, kShadeBlock, false, g, b);
 #undef RTG_SHADE
 }
-void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
-                  const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
-                  ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
-                  unsigned long long* qcount, int n, hipStream_t st,
-                  int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
-    launch_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, nodes, shadows, slist, next_rays, next_meta, qcount, n,
-                            st, gen, nq, gbase, lv_in, lv_out);
+void launch_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+                  hipStream_t st) {
+    with_pass(ps, [&](const auto& p) { launch_shade_t(sv, cam, p, seed, io, st); });
 }
-void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed,
-                  const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
-                  ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
-                  unsigned long long* qcount, int n, hipStream_t st,
-                  int gen, int nq, int gbase, const unsigned char* lv_in, unsigned char* lv_out) {
-    if (ps.plain())
-        launch_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, nodes, shadows, slist, next_rays, next_meta,
-                                qcount, n, st, gen, nq, gbase, lv_in, lv_out);
-    else
-        launch_shade_t<PassDevA>(sv, cam, level, ps, seed, rays, meta, hits, nodes, shadows, slist, next_rays, next_meta,
-                                 qcount, n, st, gen, nq, gbase, lv_in, lv_out);
+// One k_shadow launch, its variant by the traversal, the counters and the top-level BVH.  PT: a light's list
+// of the path tracer (launch_pt_shadow), else a level's Whitted list.
+template <bool PT>
+static void launch_k_shadow(const SceneView& sv, dim3 g, const ShadowPlanes& sp, bool lean, const int* slist,
+                            const unsigned* scount, const NodePlanes& np, unsigned* nan_queries, int exhaustive,
+                            Counters* ctr, int uni_from, const PtRad& pr, hipStream_t st) {
+    const dim3 b(kTraceBlock);
+    const bool tl = sv.tlas_root >= 0;
+    if (exhaustive) hipLaunchKernelGGL((k_shadow<true, false, false, PT>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, pr);
+    else if (ctr && tl) hipLaunchKernelGGL((k_shadow<false, true, true, PT>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, pr);
+    else if (ctr) hipLaunchKernelGGL((k_shadow<false, true, false, PT>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, pr);
+    else if (tl) hipLaunchKernelGGL((k_shadow<false, false, true, PT>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, pr);
+    else hipLaunchKernelGGL((k_shadow<false, false, false, PT>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, pr);
 }
-void launch_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, const unsigned* scount, NodeRec* nodes,
-                   int n, int exhaustive, Counters* ctr, unsigned* nan_queries, hipStream_t st, bool whitted, int uni_from) {
+void launch_shadow(const SceneView& sv, const StepIO& io, int exhaustive, Counters* ctr, unsigned* nan_queries,
+                   hipStream_t st) {
+    const int n = io.n;
     if (n <= 0 || sv.num_lights == 0) return;
     const long long cap = (long long)n * sv.num_lights;     // upper bound of the device-side count
-    dim3 g(nblk((int)cap, kTraceBlock)), b(kTraceBlock);
-    const NodePlanes np = node_planes(nodes, n);
-    const ShadowPlanes sp = shadow_planes(shadows, n, sv.num_lights);
-    const bool lean = whitted && sv.lean_shadow && sv.num_lights == 1;
-    const bool tl = sv.tlas_root >= 0;
-    const PtRad z{};
-    if (exhaustive) hipLaunchKernelGGL((k_shadow<true, false>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, z);
-    else if (ctr && tl) hipLaunchKernelGGL((k_shadow<false, true, true>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, z);
-    else if (ctr) hipLaunchKernelGGL((k_shadow<false, true>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, z);
-    else if (tl) hipLaunchKernelGGL((k_shadow<false, false, true>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, z);
-    else hipLaunchKernelGGL((k_shadow<false, false>), g, b, 0, st, sv, sp, lean, slist, scount, np, nan_queries, ctr, uni_from, z);
-    if (sv.num_lights > 1 && whitted)
+    const NodePlanes np = node_planes(io.nodes, n);
+    const ShadowPlanes sp = shadow_planes(io.shadows, n, sv.num_lights);
+    const bool lean = sv.lean_shadow && sv.num_lights == 1;
+    // the list's length: the high word of the step's queue counter (little endian)
+    launch_k_shadow<false>(sv, dim3(nblk((int)cap, kTraceBlock)), sp, lean, io.slist,
+                           reinterpret_cast<const unsigned*>(io.qcount) + 1, np, nan_queries, exhaustive, ctr, io.uni_from,
+                           PtRad{}, st);
+    if (sv.num_lights > 1)
         hipLaunchKernelGGL(k_light_sum, dim3(nblk(n, 256)), dim3(256), 0, st, sv, sp, np, n);
 }
-void launch_pt_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, NodeRec* nodes, int n, int exhaustive,
-                      Counters* ctr, unsigned* nan_queries, hipStream_t st, int uni_from, const PtRad& pr) {
+void launch_pt_shadow(const SceneView& sv, const StepIO& io, int exhaustive, Counters* ctr, unsigned* nan_queries,
+                      hipStream_t st) {
+    const int n = io.n;
     if (n <= 0 || sv.num_lights == 0) return;
-    dim3 g(nblk(n, kTraceBlock)), b(kTraceBlock);           // a light's list holds at most n queries
-    const NodePlanes np = node_planes(nodes, n);
-    const ShadowPlanes sp = shadow_planes(shadows, n, sv.num_lights);
-    const bool tl = sv.tlas_root >= 0;
+    const NodePlanes np = node_planes(io.nodes, n);
+    const ShadowPlanes sp = shadow_planes(io.shadows, n, sv.num_lights);
     for (int li = 0; li < sv.num_lights; li++) {
-        const int* sl = slist + (size_t)li * n;
-        const unsigned* sc = pr.lcnt + li;
-        PtRad prl = pr;
+        PtRad prl = io.pr;
         prl.light = li;
-        if (exhaustive) hipLaunchKernelGGL((k_shadow<true, false, false, true>), g, b, 0, st, sv, sp, false, sl, sc, np, nan_queries, ctr, uni_from, prl);
-        else if (ctr && tl) hipLaunchKernelGGL((k_shadow<false, true, true, true>), g, b, 0, st, sv, sp, false, sl, sc, np, nan_queries, ctr, uni_from, prl);
-        else if (ctr) hipLaunchKernelGGL((k_shadow<false, true, false, true>), g, b, 0, st, sv, sp, false, sl, sc, np, nan_queries, ctr, uni_from, prl);
-        else if (tl) hipLaunchKernelGGL((k_shadow<false, false, true, true>), g, b, 0, st, sv, sp, false, sl, sc, np, nan_queries, ctr, uni_from, prl);
-        else hipLaunchKernelGGL((k_shadow<false, false, false, true>), g, b, 0, st, sv, sp, false, sl, sc, np, nan_queries, ctr, uni_from, prl);
+        // a light's list holds at most n queries
+        launch_k_shadow<true>(sv, dim3(nblk(n, kTraceBlock)), sp, false, io.slist + (size_t)li * n, io.pr.lcnt + li, np,
+                              nan_queries, exhaustive, ctr, io.uni_from, prl, st);
     }
 }
 template <class PS>
-static void launch_pt_shade_t(const SceneView& sv, const CameraDev& cam, int level, const PS& ps, uint64_t seed,
-                              const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
-                              ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
-                              unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
-                              const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
+static void launch_pt_shade_t(const SceneView& sv, const CameraDev& cam, const PS& ps, uint64_t seed, const StepIO& io,
+                              Counters* ctr, hipStream_t st) {
+    const int n = io.n;
     if (n <= 0) return;
     dim3 g(nblk(n, kPtBlock)), b(kPtBlock);
 #define RTG_PT_LAUNCH1(F, S, B, G)                                                                                \
-    hipLaunchKernelGGL((k_pt_shade<F, S, B, G, PS>), g, b, 0, st, sv, cam, level, ps, seed, rays, meta, hits, paths, \
-                       node_planes(nodes, n), \
-                       shadow_planes(shadows, n, sv.num_lights), slist, next_rays, next_meta, next_paths, qcount, n, \
-                       nq, gbase, lv_in, lv_out, pr, ctr)
+    hipLaunchKernelGGL((k_pt_shade<F, S, B, G, PS>), g, b, 0, st, sv, cam, io.level, ps, seed, io.rays, io.meta, io.hits, io.paths, \
+                       node_planes(io.nodes, n), \
+                       shadow_planes(io.shadows, n, sv.num_lights), io.slist, io.next_rays, io.next_meta, io.next_paths, io.qcount, n, \
+                       io.nq, io.gbase, io.lv_in, io.lv_out, io.pr, ctr)
 #define RTG_PT_LAUNCH(F, S, B)                                                                                    \
     do {                                                                                                          \
-        if (gen) RTG_PT_LAUNCH1(F, S, B, true);                                                                   \
+        if (io.gen) RTG_PT_LAUNCH1(F, S, B, true);                                                                \
         else RTG_PT_LAUNCH1(F, S, B, false);                                                                      \
     } while (0)
     // textures / area / environment lights need the full variant; BRDFs alone do not
@@ -3360,25 +3350,9 @@ static void launch_pt_shade_t(const SceneView& sv, const CameraDev& cam, int lev
 #undef RTG_PT_LAUNCH
 #undef RTG_PT_LAUNCH1
 }
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
-                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
-                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
-                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
-                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
-    launch_pt_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, paths, nodes, shadows, slist, next_rays, next_meta,
-                               next_paths, qcount, n, st, gen, nq, gbase, lv_in, lv_out, pr, ctr);
-}
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed,
-                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
-                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
-                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
-                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr) {
-    if (ps.plain())
-        launch_pt_shade_t<PassDev>(sv, cam, level, ps, seed, rays, meta, hits, paths, nodes, shadows, slist, next_rays,
-                                   next_meta, next_paths, qcount, n, st, gen, nq, gbase, lv_in, lv_out, pr, ctr);
-    else
-        launch_pt_shade_t<PassDevA>(sv, cam, level, ps, seed, rays, meta, hits, paths, nodes, shadows, slist, next_rays,
-                                    next_meta, next_paths, qcount, n, st, gen, nq, gbase, lv_in, lv_out, pr, ctr);
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+                     Counters* ctr, hipStream_t st) {
+    with_pass(ps, [&](const auto& p) { launch_pt_shade_t(sv, cam, p, seed, io, ctr, st); });
 }
 void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_nodes, const NodeRec* grand_nodes, int n,
                      int n_child, int n_grand, hipStream_t st) {
@@ -3447,26 +3421,15 @@ static void launch_accumulate_t(const SceneView& sv, const NodeRec* level0, cons
     }
 }
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
-    launch_accumulate_planes_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, mom, mom_k0);
-}
-void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
                               float* acc, const PassDevA& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
-    if (ps.plain()) launch_accumulate_planes_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, mom, mom_k0);
-    else launch_accumulate_planes_t<PassDevA>(sv, level0, level1, resolve, acc, ps, nx, mode, st, mom, mom_k0);
-}
-void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
-                       const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
-                       const NodeRec* level2, int n2, float* mom, int mom_k0) {
-    launch_accumulate_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
+    with_pass(ps, [&](const auto& p) { launch_accumulate_planes_t(sv, level0, level1, resolve, acc, p, nx, mode, st, mom, mom_k0); });
 }
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
                        const PassDevA& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
                        const NodeRec* level2, int n2, float* mom, int mom_k0) {
-    if (ps.plain())
-        launch_accumulate_t<PassDev>(sv, level0, level1, resolve, acc, ps, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
-    else
-        launch_accumulate_t<PassDevA>(sv, level0, level1, resolve, acc, ps, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
+    with_pass(ps, [&](const auto& p) {
+        launch_accumulate_t(sv, level0, level1, resolve, acc, p, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
+    });
 }
 void launch_frame_error(const float* mom, int npix, int n, double* part, double* out, hipStream_t st) {
     const int nb = nblk(std::max(npix, 1), kErrBlock);

@@ -1109,8 +1109,8 @@ struct Lane {
     hipStream_t st = nullptr;
     hipEvent_t ev_count = nullptr;          // recorded after the level count copy
     hipEvent_t ev_join = nullptr;           // stream schedule: the lane's work of a segment is done
-    hipEvent_t ev_t[6] = {};                // trace start, trace end, shade end, shadow start, shadow end,
-                                            // path-tracer gather end
+    hipEvent_t ev_t[5] = {};                // collect_timing: trace start, trace end, shade end, shadow start,
+                                            // shadow end (Render::step); timed_launch brackets with 0 and 1
     unsigned long long* h_count = nullptr;  // pinned host slot
     DBuf qcnt;                              // 128 x u64 per pass: [level] next rays | shadow entries << 32
     DBuf lcnt;                              // path tracer: per-light shadow-list counts per level / step
@@ -1119,12 +1119,12 @@ struct Lane {
     // current pass
     std::vector<int> passes;                // indices into the frame's pass list (this lane's, in order)
     size_t next_pass = 0;
-    bool busy = false;
-    int pass = -1, level = 0;
+    int pass = -1, level = 0;               // level: of the current pass; stream schedule: the lane's steps of
+                                            // the segment so far (the index of its next step)
     std::vector<int> counts;
-    // stream schedule: the current step's queued (survivor) and total ray counts, and the steps run
-    // since the lane last took new samples
-    int sq = 0, sn = 0, sdrain = 0;
+    // stream schedule: the current step's total ray count, and the steps run since the lane last took
+    // new samples
+    int sn = 0, sdrain = 0;
     std::vector<DBuf> snodes;                // reference integrator: node records of each step of a segment
     std::vector<int> step_m, step_g, step_gb;   // ... and each step's survivors, new samples, first new slot
     int create() {
@@ -2485,31 +2485,157 @@ static CameraDev make_camera(const rtg_camera_desc* c) {
     return k;
 }
 
-static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, float* out_dev,
-                       hipStream_t st, const RenderTarget* target = nullptr) {
-    if (cam->nx < 1 || cam->ny < 1 || cam->num_samples < 1) return fail(RTG_ERR_INVALID, "bad camera");
+}  // extern "C"
+
+// Grow the scene's lanes to n.
+static int ensure_lanes(rtg_scene* s, int n) {
+    while ((int)s->lanes.size() < n) {
+        s->lanes.emplace_back();
+        const int rc = s->lanes.back().create();
+        if (rc) { s->lanes.back().destroy(); s->lanes.pop_back(); return rc; }
+    }
+    return RTG_OK;
+}
+
+// The pixel order of a render (tile_pixel), from its options and camera: the shard's rows, the tile height
+// and the band height.  One rule for the render loop, a frame's active list (tile-order indices, which are
+// only right while the two agree) and the feature buffers; a pass adds its ranges (s0 / ns / p0 / npass).
+// The order: bands 16 tiles high, walked in columns of tiles.  1080p64 dragon,
+// one-tile-high bands -> 16: k_trace 14.7 -> 13.3 ms, k_shadow 13.1 -> 12.3 ms per frame, frame
+// 36.9 -> 36.0 ms; a 1/8 row shard 5.6 -> 5.1 ms (its passes become blocks of columns instead of
+// row strips, so each holds a mix of sky, floor and glass).  4 / 8 / 32 / 64 tiles: in between.
+static int pixel_order(const rtg_render_opts& o, const rtg_camera_desc* cam, PassDevA& ps) {
+    const int stride = o.row_stride > 1 ? o.row_stride : 1, block = o.row_block > 1 ? o.row_block : 1;
+    if (o.row_offset < 0 || o.row_offset >= stride) return fail(RTG_ERR_INVALID, "row_offset out of range");
+    const int rows_owned = rtg_shard_rows(cam->ny, o.row_offset, stride, block);
+    if ((long long)rows_owned * cam->nx > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
+    ps.row_offset = o.row_offset; ps.row_stride = stride; ps.rows_owned = rows_owned; ps.row_block = block;
+    // Band height (round 6, VERDICT r5 #6): kBandRows owned rows, whatever the tile height -- bands of
+    // 8 tiles for the full frame's 8-row tiles and 16 for a row shard's 4-row tiles, which are the optima
+    // round 5 found by sweeping each case separately (`profiles/history/r6_ab_schedule_sweep.jsonl`,
+    // `r6_shard_band.txt`: 1/8 dragon shard 5.39 ms with 32-row bands, 4.40 with 64); one rule instead of
+    // a special case for shards (its measurements per N: profiles/r7/shard_probe*.txt).
+    ps.tile_h = stride > 1 && block < 8 ? (block >= 4 ? 4 : block >= 2 ? 2 : 1) : 8;
+    const int tile_s = o.tile_band > 0 ? std::min(o.tile_band, 1 << 12) : std::max(1, kBandRows / ps.tile_h);
+    // tile_pixel (device) forms band * (tile_h * tile_s * nx) in 32-bit ints: keep one band of the
+    // widest tiles (tile_h <= 8) below 2^31 pixels
+    if ((long long)8 * cam->nx >= (1LL << 31)) return fail(RTG_ERR_UNSUPPORTED, "image wider than 2^28 pixels");
+    ps.tile_s = (int)std::min<long long>(tile_s, ((1LL << 31) - 1) / (8LL * cam->nx));
+    return RTG_OK;
+}
+
+namespace {
+
+// One render on one device (render_impl): the plan -- everything the options, the camera, the scene and
+// the device's memory decide before a launch -- the step and the drain that both schedules share, and the
+// two schedules.
+struct Render {
+    rtg_scene* s;
+    const rtg_camera_desc* cam;
     rtg_render_opts o{};
+    RenderTarget tg{};
+    CameraDev cd{};
+    SceneView sv{};                    // per-render view: the path tracer's light loop
+    PassDevA order{};                  // the pixel order and the target's list / sample order: every pass's base
+    // plan
+    int npix = 0, total = 0;           // npix: pixel ordinals (an adaptive frame: its active pixels, §15); total: samples per pixel of this call
+    bool pt = false, timing = false, stream = false;
+    int nL = 0, max_levels = 0, exhaustive = 0;
+    int lanes = 0;                     // lanes in flight, of the schedule that runs
+    int ns_chunk = 0, np_pass = 0;     // pass schedule: samples and pixels of a pass
+    long long R = 0;                   // stream schedule: rays per step,
+    int seg_np = 0;                    // pixels of a segment (path tracer),
+    double node_budget = 0.0;          // node-record bytes that close a segment (reference integrator)
+    // run
+    unsigned* d_cnt = nullptr;         // d_cnt[0]: NaN shadow queries (all passes)
+    Counters* sctr = nullptr;
+    rtg_render_stats stt{};
+    uint64_t shadow_listed = 0;
+    std::deque<int> waiting;           // lanes with a step in flight, in enqueue order
+    std::vector<PassDevA> plist;       // pass schedule: the frame's passes
+    struct {                           // stream schedule: the frame's slot cursor and the open segment
+        PassDevA F;
+        long long cursor = 0, end = 0, slots = 0;
+        double node_bytes = 0.0;
+        bool closed = false;
+    } seg;
+
+    Render(rtg_scene* s_, const rtg_camera_desc* cam_) : s(s_), cam(cam_) {}
+    int plan(const rtg_render_opts* opts, const RenderTarget* target);
+    int step(Lane& ln, const PassDevA& ps, const StepIO& io);
+    int drain(int& k, unsigned& next);
+    int run_passes();
+    int level_step(Lane& ln);
+    int start_pass(Lane& ln);
+    int finish_pass(Lane& ln);
+    int run_stream();
+    int stream_step(Lane& ln, int m, int g);
+    int new_samples(long long m) const;
+    void fill_stats(float ms, unsigned nan_queries, const Counters& ctr);
+
+    // collect_timing: one launch between two events, waited for (roofline frames only)
+    template <class F>
+    int timed_launch(Lane& ln, F&& launch, double& ms, int& launches) {
+        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[0], ln.st));
+        launch();
+        if (timing) {
+            float a = 0.0f;
+            HIP_TRY(hipEventRecord(ln.ev_t[1], ln.st));
+            HIP_TRY(hipEventSynchronize(ln.ev_t[1]));
+            HIP_TRY(hipEventElapsedTime(&a, ln.ev_t[0], ln.ev_t[1]));
+            ms += a;
+            launches++;
+        }
+        return RTG_OK;
+    }
+};
+
+int Render::plan(const rtg_render_opts* opts, const RenderTarget* target) {
+    if (cam->nx < 1 || cam->ny < 1 || cam->num_samples < 1) return fail(RTG_ERR_INVALID, "bad camera");
     if (opts) o = *opts;
     if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_INVALID, "num_devices / devices need rtg_render / rtg_render_device");
-    int stride = o.row_stride > 1 ? o.row_stride : 1;
-    int off = o.row_offset;
-    if (off < 0 || off >= stride) return fail(RTG_ERR_INVALID, "row_offset out of range");
-    const int block = o.row_block > 1 ? o.row_block : 1;
-    CameraDev cd = make_camera(cam);
-    const int rows_owned = rtg_shard_rows(cam->ny, off, stride, block);
-    long long npix_ll = (long long)rows_owned * cam->nx;
-    if (npix_ll > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
-    int npix = (int)npix_ll;
-    RenderTarget tg = target ? *target : RenderTarget{nullptr, nullptr, 0, cam->num_samples, 0}; const int total = tg.ns; if (tg.active) npix = tg.nactive;   // total: samples per pixel of this call; npix: pixel ordinals (an adaptive frame: its active pixels, §15)
+    int rc;
+    if ((rc = pixel_order(o, cam, order))) return rc;
+    tg = target ? *target : RenderTarget{nullptr, nullptr, 0, cam->num_samples, 0};
+    total = tg.ns;
+    npix = tg.active ? tg.nactive : order.rows_owned * cam->nx;
+    order.active = tg.active; order.ord_m = tg.ord_m; order.ord_n = tg.ord_n;
     if (cam->integrator != RTG_INTEGRATOR_REFERENCE && cam->integrator != RTG_INTEGRATOR_PATH)
         return fail(RTG_ERR_INVALID, "unknown integrator");
-    const bool pt = cam->integrator == RTG_INTEGRATOR_PATH;
-    SceneView sv = s->sv;                    // per-render view: the path tracer's light loop
+    if (o.tile_band < 0 || o.segment_pixels < 0 || o.segment_nodes < 0)
+        return fail(RTG_ERR_INVALID, "tile_band / segment_pixels / segment_nodes");
+    if (o.schedule < RTG_SCHEDULE_AUTO || o.schedule > RTG_SCHEDULE_STREAM) return fail(RTG_ERR_INVALID, "schedule");
+    pt = cam->integrator == RTG_INTEGRATOR_PATH;
+    cd = make_camera(cam);
+    sv = s->sv;
     if (pt) {
         sv.pt_flags = cam->pt_flags;
         if (cam->pt_flags & RTG_PT_NEE) sv.num_lights += s->num_emit;
     }
-    const int nL = sv.num_lights;
+    nL = sv.num_lights;
+    max_levels = (pt && (cam->pt_flags & RTG_PT_RUSSIAN_ROULETTE)) ? RTG_PT_MAX_BOUNCES : std::max(0, s->sv.max_depth) + 1;
+    exhaustive = o.traversal == 1;
+    timing = o.collect_timing != 0;
+    size_t free_b = 0, dev_total_b = 0;
+    if (hipMemGetInfo(&free_b, &dev_total_b) != hipSuccess) dev_total_b = 0;
+    const long long frame_rays = (long long)npix * total;
+    stream = (o.schedule == RTG_SCHEDULE_STREAM || (o.schedule == RTG_SCHEDULE_AUTO && pt)) && npix > 0 &&
+             frame_rays < (1LL << 31);
+    if (stream) {
+        lanes = o.streams > 0 ? std::min(o.streams, 8) : s->stream_lanes;
+        // rays per step: an even share of the frame, about s->stream_div new-sample steps per lane,
+        // within the memory cap of a pass
+        const long long kR = rtg_pass_rays(nL, pt ? 1 : 0, lanes, (uint64_t)dev_total_b);
+        const long long share = (frame_rays + (long long)lanes * s->stream_div - 1) / ((long long)lanes * s->stream_div);
+        R = o.max_batch_rays > 0 ? std::max<long long>(64, o.max_batch_rays)
+                                 : std::max<long long>(std::min<long long>(kR, 1LL << 16), std::min(kR, share));
+        const long long rad_slots = std::max<long long>(total, (long long)(dev_total_b ? dev_total_b / 8 / 16 : 1LL << 28));
+        seg_np = pt ? (int)std::max<long long>(1, std::min<long long>(npix, rad_slots / total)) : npix;
+        if (pt && o.segment_pixels > 0) seg_np = std::min(seg_np, o.segment_pixels);
+        node_budget = o.segment_nodes > 0 ? (double)sizeof(NodeRec) * o.segment_nodes
+                                          : (dev_total_b ? 0.25 * (double)dev_total_b : 16e9);
+        return RTG_OK;
+    }
     // auto batch: a whole multiple of the lanes in flight, as few passes as the ray cap allows,
     // at least 2M rays each -- every lane gets the same number of equal passes, so the lanes'
     // level tails end together and overlap each other's work (1080p64 dragon, passes x lanes:
@@ -2517,22 +2643,13 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     // 3x3 -> 8x8 9.15 -> 8.1 ms).  The cap is 24M rays, lowered so that every lane's level buffers
     // fit half the device memory (rtg_pass_rays: many lights cost 68 B per ray and light).
     const int lanes_req = o.streams > 0 ? std::min(o.streams, 8) : s->num_lanes;
-    const long long frame_rays = (long long)npix * total;
-    int ns_chunk, np_pass;
-    size_t dev_total_b = 0;
-    {
-        size_t free_b = 0;
-        if (hipMemGetInfo(&free_b, &dev_total_b) != hipSuccess) dev_total_b = 0;
-    }
     if (o.max_batch_rays > 0) {
         const long long max_batch = o.max_batch_rays;
         // passes: all samples of a pixel range (chunks of samples only when spp exceeds the batch)
         ns_chunk = (int)std::max<long long>(1, std::min<long long>(total, max_batch));
         np_pass = (int)std::max<long long>(1, std::min<long long>(npix, max_batch / ns_chunk));
     } else {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = 0;
-        const long long kMax = rtg_pass_rays(nL, pt ? 1 : 0, lanes_req, (uint64_t)total_b);
+        const long long kMax = rtg_pass_rays(nL, pt ? 1 : 0, lanes_req, (uint64_t)dev_total_b);
         const long long kMin = std::min<long long>(2LL << 20, kMax);
         const long long lanes_eff = std::max(1LL, std::min<long long>(lanes_req, (frame_rays + kMin - 1) / kMin));
         // (an empty shard -- fewer row blocks than ranks -- has no rays: one empty pass, not a division by 0)
@@ -2545,525 +2662,190 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             np_pass = (int)std::max<long long>(1, (npix + passes - 1) / passes);   // `passes` pixel ranges
         }
     }
-    int exhaustive = o.traversal == 1;
+    const int nranges = npix > 0 ? (npix + np_pass - 1) / np_pass : 1;
+    lanes = std::max(1, std::min(lanes_req, nranges));
+    return RTG_OK;
+}
 
+// Enqueue one step on its lane: trace, shade, the count read-back, the shadow queries -- a level of a pass
+// or a step of the stream schedule; the schedule fills `io` from its own buffers.
+int Render::step(Lane& ln, const PassDevA& ps, const StepIO& io) {
+    if (timing) HIP_TRY(hipEventRecord(ln.ev_t[0], ln.st));
+    // (primary rays are generated inside k_trace / k_shade / k_pt_shade: there is no level-0 ray buffer)
+    launch_trace(sv, cd, ps, o.seed, io, exhaustive, sctr, ln.st);
+    if (timing) HIP_TRY(hipEventRecord(ln.ev_t[1], ln.st));
+    if (pt) launch_pt_shade(sv, cd, ps, o.seed, io, sctr, ln.st);
+    else launch_shade(sv, cd, ps, o.seed, io, ln.st);
+    if (timing) HIP_TRY(hipEventRecord(ln.ev_t[2], ln.st));
+    // the next step's size is known once shade is done: read it back now, so the host can
+    // enqueue that step while this one's shadow queries still run (no host round trip
+    // between the steps on the stream)
+    HIP_TRY(hipMemcpyAsync(ln.h_count, io.qcount, sizeof(unsigned long long), hipMemcpyDeviceToHost, ln.st));
+    HIP_TRY(hipEventRecord(ln.ev_count, ln.st));
+    if (timing) HIP_TRY(hipEventRecord(ln.ev_t[3], ln.st));
+    // (the path tracer: one launch per light, in light order, adding each vertex's T (x) v to its
+    // sample's running radiance -- PtRad; no gather kernel)
+    if (pt) launch_pt_shadow(sv, io, exhaustive, sctr, d_cnt, ln.st);
+    else launch_shadow(sv, io, exhaustive, sctr, d_cnt, ln.st);
+    if (timing) HIP_TRY(hipEventRecord(ln.ev_t[4], ln.st));
+    HIP_TRY(hipGetLastError());
+    return RTG_OK;
+}
+
+// Take the next lane to service off `waiting` -- the first (in enqueue order) whose count read-back has
+// landed, so a lane with a long step does not hold up the others (head-of-line blocking) -- and read its
+// step's count (next: the rays it queued) and times.
+int Render::drain(int& k, unsigned& next) {
+    size_t pick = 0;
+    while (waiting.size() > 1) {       // (a single lane: wait for it)
+        for (pick = 0; pick < waiting.size(); pick++) {
+            const hipError_t q = hipEventQuery(s->lanes[waiting[pick]].ev_count);
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) HIP_TRY(q);
+        }
+        if (pick < waiting.size()) break;
+        pick = 0;
+        std::this_thread::yield();
+    }
+    k = waiting[pick];
+    waiting.erase(waiting.begin() + pick);
+    Lane& ln = s->lanes[k];
+    HIP_TRY(hipEventSynchronize(ln.ev_count));
+    const unsigned long long q = *ln.h_count;
+    next = (unsigned)q;
+    shadow_listed += q >> 32;
+    if (timing) {
+        float a = 0.0f, b = 0.0f, c = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&a, ln.ev_t[0], ln.ev_t[1]));
+        HIP_TRY(hipEventElapsedTime(&c, ln.ev_t[1], ln.ev_t[2]));
+        stt.trace_ms += a;
+        stt.trace_launches++;
+        stt.shade_ms += c;
+        stt.shade_launches++;
+        if (nL > 0) {
+            HIP_TRY(hipEventSynchronize(ln.ev_t[4]));   // the count arrives before the shadow pass ends
+            HIP_TRY(hipEventElapsedTime(&b, ln.ev_t[3], ln.ev_t[4]));
+            stt.shadow_ms += b;
+            stt.shadow_launches++;
+        }
+    }
+    return RTG_OK;
+}
+
+// ------------------------------------------------------------ pass schedule
+// trace / shade / shadow of the lane's current level
+int Render::level_step(Lane& ln) {
+    const int level = ln.level;
+    const int n = ln.counts[level];
+    if ((int)ln.levels.size() < level + 2) ln.levels.resize(level + 2);
+    Level& Lc = ln.levels[level];
+    Level& Ln = ln.levels[level + 1];
     int rc;
-    if (!tg.acc) { if ((rc = s->d_acc.grow(sizeof(float) * 3 * std::max<size_t>(npix, 1)))) return rc; tg.acc = s->d_acc.as<float>(); }
-    // d_cnt[0]: NaN shadow queries (all passes)
-    if ((rc = s->d_counters.grow(sizeof(unsigned) * 64))) return rc;
-    if ((rc = s->d_stats.grow(sizeof(Counters)))) return rc;
-    unsigned* d_cnt = s->d_counters.as<unsigned>();
-    Counters* d_stats = s->d_stats.as<Counters>();
-    HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, sizeof(unsigned) * 64, st));
-    HIP_TRY(hipMemsetAsync(s->d_stats.p, 0, sizeof(Counters), st));
-    uint64_t shadow_listed = 0;
+    if ((rc = Lc.hits.grow(std::max(sizeof(HitRec), kHitBytes) * (size_t)n)) || (rc = Lc.nodes.grow(sizeof(NodeRec) * (size_t)n)) ||
+        (rc = Lc.shadows.grow(sizeof(ShadowRec) * (size_t)n * std::max(nL, 1))) ||
+        (rc = Lc.slist.grow(sizeof(int) * (size_t)n * std::max(nL, 1))))
+        return rc;
+    const bool may_spawn = level + 1 < max_levels;
+    const size_t cap = may_spawn ? 2 * (size_t)n : 1;
+    if ((rc = Ln.rays.grow(kRayBytes * cap)) || (rc = Ln.meta.grow(sizeof(RayMeta) * cap))) return rc;
+    Ln.rcap = (long long)cap;
+    if (pt && ((rc = Lc.paths.grow(sizeof(PathRec) * (size_t)n)) || (rc = Ln.paths.grow(sizeof(PathRec) * cap)) ||
+               (rc = Lc.carry.grow(kCarryBytes * (size_t)n)) || (rc = Ln.carry.grow(kCarryBytes * cap))))
+        return rc;
+    StepIO io{};
+    io.gen = level == 0;               // level 0: the pass's primary rays
+    io.rays = io.gen ? RayQ{} : ray_planes(Lc.rays.p, Lc.rcap, sv.has_blur);
+    io.meta = io.gen ? nullptr : Lc.meta.as<RayMeta>();
+    io.hits = Lc.hits.as<HitRec>(); io.paths = Lc.paths.as<PathRec>(); io.nodes = Lc.nodes.as<NodeRec>();
+    io.shadows = Lc.shadows.as<ShadowRec>(); io.slist = Lc.slist.as<int>();
+    io.next_rays = ray_planes(Ln.rays.p, Ln.rcap, sv.has_blur);
+    io.next_meta = Ln.meta.as<RayMeta>(); io.next_paths = Ln.paths.as<PathRec>();
+    io.qcount = ln.qcnt.as<unsigned long long>() + level;
+    io.n = n; io.nq = io.gen ? 0 : n; io.level = level;
+    if (pt)
+        io.pr = PtRad{Lc.carry.as<float4>(), Ln.carry.as<float4>(), ln.prad.as<float4>(),
+                      ln.lcnt.as<unsigned>() + (size_t)level * std::max(nL, 1)};
+    io.uni_from = level < kUniShadowLevels ? 0 : INT_MAX;
+    return step(ln, plist[ln.pass], io);
+}
 
-    struct Events {                     // RAII: released on every return path
-        hipEvent_t e[3] = {};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-    hipEvent_t e0 = ev.e[0], e1 = ev.e[1], ejoin = ev.e[2];
-    HIP_TRY(hipEventRecord(e0, st));
-    const bool timing = o.collect_timing != 0;
-    Counters* sctr = o.collect_stats ? d_stats : nullptr;
+int Render::start_pass(Lane& ln) {
+    ln.pass = ln.passes[ln.next_pass++];
+    const PassDevA& ps = plist[ln.pass];
+    const int n0 = ps.ns * ps.npass;
+    int rc;
+    if ((rc = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc;
+    HIP_TRY(hipMemsetAsync(ln.qcnt.p, 0, sizeof(unsigned long long) * 128, ln.st));
+    if (pt) {
+        const size_t nlc = (size_t)(max_levels + 1) * std::max(nL, 1);
+        if ((rc = ln.prad.grow((size_t)16 * std::max(n0, 1))) || (rc = ln.lcnt.grow(sizeof(unsigned) * nlc))) return rc;
+        HIP_TRY(hipMemsetAsync(ln.lcnt.p, 0, sizeof(unsigned) * nlc, ln.st));
+    }
+    ln.counts.assign(1, n0);
+    ln.level = 0;
+    // both integrators generate their primary rays inside level 0's kernels (primary_ray)
+    stt.primary_rays += (uint64_t)n0;
+    return level_step(ln);
+}
 
+int Render::finish_pass(Lane& ln) {
+    const PassDevA& ps = plist[ln.pass];
+    const int level = ln.level;
+    stt.max_level = std::max(stt.max_level, level);
+    int rc;
+    // bottom-up (round 5): levels level-1 .. 2 two at a time (k_resolve2: a level and, inline, its
+    // children, which no one else reads), the odd one alone, and levels 1 and 0 inside the
+    // accumulation -- every resolved level is stored only where its parents are not resolved
+    // in the same launch.  The nodes of `level` itself are final.
+    auto N = [&](int l) { return ln.levels[l].nodes.as<NodeRec>(); };
+    int l = level - 1;
+    for (; l >= 3 && !pt; l -= 2)
+        if ((rc = timed_launch(ln, [&] {
+                 launch_resolve2(sv, N(l - 1), N(l), N(l + 1), ln.counts[l - 1], ln.counts[l], ln.counts[l + 1], ln.st);
+             }, stt.resolve_ms, stt.resolve_launches)))
+            return rc;
+    if (l == 2 && !pt &&
+        (rc = timed_launch(ln, [&] { launch_resolve(sv, N(2), N(3), ln.counts[2], ln.counts[3], ln.st); },
+                           stt.resolve_ms, stt.resolve_launches)))
+        return rc;
+    const int before = tg.have + (ps.s0 - tg.s0), mode = (cam->num_samples == 1) ? 2 : (before == 0 ? 1 : 0);   // before: samples already summed
+    const NodeRec* level1 = level >= 1 ? N(1) : nullptr;
+    const NodeRec* level2 = level >= 2 ? N(2) : nullptr;
+    if ((rc = timed_launch(ln, [&] {
+             // (the path tracer: the pass's sample radiance, PtRad)
+             launch_accumulate(sv, pt ? ln.prad.as<NodeRec>() : N(0), level1, !pt && level >= 1, tg.acc, ps,
+                               cam->nx, mode, ln.st, !pt,
+                               ln.counts[0], level >= 1 ? ln.counts[1] : 0, pt ? nullptr : level2,
+                               level >= 2 ? ln.counts[2] : 0, tg.mom, before);
+         }, stt.accumulate_ms, stt.accumulate_launches)))
+        return rc;
+    stt.passes++;
+    return RTG_OK;
+}
+
+int Render::run_passes() {
     // the frame's passes: pixel ranges (outer) x sample chunks (inner); all chunks of one pixel
     // range go to the same lane, in order (the in-order sum of MultiSample, src/Scene.cpp:386-409)
-    // pixel order (tile_pixel): bands 16 tiles high, walked in columns of tiles.  1080p64 dragon,
-    // one-tile-high bands -> 16: k_trace 14.7 -> 13.3 ms, k_shadow 13.1 -> 12.3 ms per frame, frame
-    // 36.9 -> 36.0 ms; a 1/8 row shard 5.6 -> 5.1 ms (its passes become blocks of columns instead of
-    // row strips, so each holds a mix of sky, floor and glass).  4 / 8 / 32 / 64 tiles: in between.
-    if (o.tile_band < 0 || o.segment_pixels < 0 || o.segment_nodes < 0)
-        return fail(RTG_ERR_INVALID, "tile_band / segment_pixels / segment_nodes");
-    // Band height (round 6, VERDICT r5 #6): kBandRows owned rows, whatever the tile height -- bands of
-    // 8 tiles for the full frame's 8-row tiles and 16 for a row shard's 4-row tiles, which are the optima
-    // round 5 found by sweeping each case separately (`profiles/history/r6_ab_schedule_sweep.jsonl`,
-    // `r6_shard_band.txt`: 1/8 dragon shard 5.39 ms with 32-row bands, 4.40 with 64); one rule instead of
-    // a special case for shards (its measurements per N: profiles/r7/shard_probe*.txt).
-    const int tile_h = stride > 1 && block < 8 ? (block >= 4 ? 4 : block >= 2 ? 2 : 1) : 8;
-    int tile_s = o.tile_band > 0 ? std::min(o.tile_band, 1 << 12) : std::max(1, kBandRows / tile_h);
-    // tile_pixel (device) forms band * (tile_h * tile_s * nx) in 32-bit ints: keep one band of the
-    // widest tiles (tile_h <= 8) below 2^31 pixels
-    if ((long long)8 * cam->nx >= (1LL << 31)) return fail(RTG_ERR_UNSUPPORTED, "image wider than 2^28 pixels");
-    tile_s = (int)std::min<long long>(tile_s, ((1LL << 31) - 1) / (8LL * cam->nx));
-    std::vector<PassDevA> plist;
+    for (int k = 0; k < lanes; k++) { s->lanes[k].passes.clear(); s->lanes[k].next_pass = 0; }
     for (int p0 = 0; p0 < npix; p0 += np_pass)
         for (int s0 = 0; s0 < total; s0 += ns_chunk) {
-            PassDevA ps;
+            PassDevA ps = order;
             ps.s0 = tg.s0 + s0; ps.ns = std::min(ns_chunk, total - s0);
             ps.p0 = p0; ps.npass = std::min(np_pass, npix - p0);
-            ps.row_offset = off; ps.row_stride = stride; ps.rows_owned = rows_owned; ps.row_block = block;
-            ps.tile_h = tile_h; ps.active = tg.active;
-            ps.tile_s = tile_s; ps.ord_m = tg.ord_m; ps.ord_n = tg.ord_n;
+            s->lanes[(p0 / np_pass) % lanes].passes.push_back((int)plist.size());
             plist.push_back(ps);
         }
-    const int nranges = npix > 0 ? (npix + np_pass - 1) / np_pass : 1;
-    const int want_lanes = std::max(1, std::min(o.streams > 0 ? std::min(o.streams, 8) : s->num_lanes, nranges));
-    while ((int)s->lanes.size() < want_lanes) {
-        s->lanes.emplace_back();
-        if ((rc = s->lanes.back().create())) { s->lanes.back().destroy(); s->lanes.pop_back(); return rc; }
-    }
-    const int L = want_lanes;
-    for (int k = 0; k < L; k++) {
-        Lane& ln = s->lanes[k];
-        ln.passes.clear(); ln.next_pass = 0; ln.busy = false;
-        HIP_TRY(hipStreamWaitEvent(ln.st, e0, 0));
-    }
-    for (size_t k = 0; k < plist.size(); k++) {
-        const int prange = plist[k].p0 / np_pass;
-        s->lanes[prange % L].passes.push_back((int)k);
-    }
-
-    rtg_render_stats stt{};
-    const int max_levels = (pt && (cam->pt_flags & RTG_PT_RUSSIAN_ROULETTE)) ? RTG_PT_MAX_BOUNCES
-                                                                             : std::max(0, s->sv.max_depth) + 1;
-    // enqueue trace / shade / shadow of the lane's current level and the count read-back
-    auto enqueue_level = [&](Lane& ln) -> int {
-        const PassDevA& ps = plist[ln.pass];
-        const int level = ln.level;
-        const int n = ln.counts[level];
-        if ((int)ln.levels.size() < level + 2) ln.levels.resize(level + 2);
-        Level& Lc = ln.levels[level];
-        Level& Ln = ln.levels[level + 1];
-        int rc2;
-        if ((rc2 = Lc.hits.grow(std::max(sizeof(HitRec), kHitBytes) * (size_t)n)) || (rc2 = Lc.nodes.grow(sizeof(NodeRec) * (size_t)n)) ||
-            (rc2 = Lc.shadows.grow(sizeof(ShadowRec) * (size_t)n * std::max(nL, 1))) ||
-            (rc2 = Lc.slist.grow(sizeof(int) * (size_t)n * std::max(nL, 1))))
-            return rc2;
-        const bool may_spawn = level + 1 < max_levels;
-        const size_t cap = may_spawn ? 2 * (size_t)n : 1;
-        if ((rc2 = Ln.rays.grow(kRayBytes * cap)) || (rc2 = Ln.meta.grow(sizeof(RayMeta) * cap))) return rc2;
-        Ln.rcap = (long long)cap;
-        const RayQ cur_q = level == 0 ? RayQ{} : ray_planes(Lc.rays.p, Lc.rcap, sv.has_blur);
-        const RayQ next_q = ray_planes(Ln.rays.p, Ln.rcap, sv.has_blur);
-        if (pt && ((rc2 = Lc.paths.grow(sizeof(PathRec) * (size_t)n)) || (rc2 = Ln.paths.grow(sizeof(PathRec) * cap)) ||
-                   (rc2 = Lc.carry.grow(kCarryBytes * (size_t)n)) || (rc2 = Ln.carry.grow(kCarryBytes * cap))))
-            return rc2;
-        unsigned long long* qc = ln.qcnt.as<unsigned long long>() + level;
-        const PtRad pr = pt ? PtRad{Lc.carry.as<float4>(), Ln.carry.as<float4>(), ln.prad.as<float4>(),
-                                    ln.lcnt.as<unsigned>() + (size_t)level * std::max(nL, 1)}
-                            : PtRad{};
-        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[0], ln.st));
-        // level 0: k_trace / k_shade / k_pt_shade regenerate the primary rays (no level-0 ray buffer)
-        const bool gen = level == 0;
-        launch_trace(sv, cur_q, Lc.hits.as<HitRec>(), n, exhaustive, sctr, ln.st,
-                     gen ? &cd : nullptr, gen ? &ps : nullptr, o.seed, /*compact=*/true);
-        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[1], ln.st));
-        if (pt)
-            launch_pt_shade(sv, cd, level, ps, o.seed, cur_q,
-                            gen ? nullptr : Lc.meta.as<RayMeta>(), Lc.hits.as<HitRec>(),
-                            Lc.paths.as<PathRec>(), Lc.nodes.as<NodeRec>(), Lc.shadows.as<ShadowRec>(), Lc.slist.as<int>(),
-                            next_q, Ln.meta.as<RayMeta>(), Ln.paths.as<PathRec>(), qc, n, ln.st,
-                            gen, gen ? 0 : n, 0, nullptr, nullptr, pr, sctr);
-        else
-            launch_shade(sv, cd, level, ps, o.seed, cur_q,
-                         gen ? nullptr : Lc.meta.as<RayMeta>(), Lc.hits.as<HitRec>(),
-                         Lc.nodes.as<NodeRec>(), Lc.shadows.as<ShadowRec>(), Lc.slist.as<int>(), next_q,
-                         Ln.meta.as<RayMeta>(), qc, n, ln.st);
-        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[2], ln.st));
-        // the next level's size is known once shade is done: read it back now, so the host can
-        // enqueue that level while this level's shadow queries still run (no host round trip
-        // between the levels on the stream)
-        HIP_TRY(hipMemcpyAsync(ln.h_count, qc, sizeof(unsigned long long), hipMemcpyDeviceToHost, ln.st));
-        HIP_TRY(hipEventRecord(ln.ev_count, ln.st));
-        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[3], ln.st));
-        // (the path tracer: one launch per light, in light order, adding each vertex's T (x) v to its
-        // sample's running radiance -- PtRad; no gather kernel)
-        if (pt)
-            launch_pt_shadow(sv, Lc.shadows.as<ShadowRec>(), Lc.slist.as<int>(), Lc.nodes.as<NodeRec>(), n, exhaustive,
-                             sctr, d_cnt, ln.st, /*uni_from=*/level < kUniShadowLevels ? 0 : INT_MAX, pr);
-        else
-            launch_shadow(sv, Lc.shadows.as<ShadowRec>(), Lc.slist.as<int>(),
-                          reinterpret_cast<const unsigned*>(qc) + 1,   // high word (little endian)
-                          Lc.nodes.as<NodeRec>(), n, exhaustive, sctr, d_cnt, ln.st, /*light_sum=*/true,
-                          /*uni_from=*/level < kUniShadowLevels ? 0 : INT_MAX);
-        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[4], ln.st));
-        HIP_TRY(hipGetLastError());
-        return RTG_OK;
-    };
-    auto start_pass = [&](Lane& ln) -> int {
-        ln.pass = ln.passes[ln.next_pass++];
-        const PassDevA& ps = plist[ln.pass];
-        const int n0 = ps.ns * ps.npass;
-        int rc2;
-        if ((rc2 = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc2;
-        HIP_TRY(hipMemsetAsync(ln.qcnt.p, 0, sizeof(unsigned long long) * 128, ln.st));
-        if (pt) {
-            const size_t nlc = (size_t)(max_levels + 1) * std::max(nL, 1);
-            if ((rc2 = ln.prad.grow((size_t)16 * std::max(n0, 1))) || (rc2 = ln.lcnt.grow(sizeof(unsigned) * nlc))) return rc2;
-            HIP_TRY(hipMemsetAsync(ln.lcnt.p, 0, sizeof(unsigned) * nlc, ln.st));
-        }
-        ln.counts.assign(1, n0);
-        ln.level = 0;
-        if ((int)ln.levels.size() < 1) ln.levels.resize(1);
-        // both integrators generate their primary rays inside level 0's kernels (primary_ray)
-        stt.primary_rays += (uint64_t)n0;
-        ln.busy = true;
-        return enqueue_level(ln);
-    };
-    // collect_timing: one launch between two events, waited for (roofline frames only)
-    auto timed_launch = [&](Lane& ln, auto&& launch, double& ms, int& launches) -> int {
-        if (timing) HIP_TRY(hipEventRecord(ln.ev_t[0], ln.st));
-        launch();
-        if (timing) {
-            float a = 0.0f;
-            HIP_TRY(hipEventRecord(ln.ev_t[1], ln.st));
-            HIP_TRY(hipEventSynchronize(ln.ev_t[1]));
-            HIP_TRY(hipEventElapsedTime(&a, ln.ev_t[0], ln.ev_t[1]));
-            ms += a;
-            launches++;
-        }
-        return RTG_OK;
-    };
-    auto finish_pass = [&](Lane& ln) -> int {
-        const PassDevA& ps = plist[ln.pass];
-        const int level = ln.level;
-        stt.max_level = std::max(stt.max_level, level);
-        int rc2;
-        // bottom-up (round 5): levels level-1 .. 2 two at a time (k_resolve2: a level and, inline, its
-        // children, which no one else reads), the odd one alone, and levels 1 and 0 inside the
-        // accumulation -- every resolved level is stored only where its parents are not resolved
-        // in the same launch.  The nodes of `level` itself are final.
-        auto N = [&](int l) { return ln.levels[l].nodes.as<NodeRec>(); };
-        int l = level - 1;
-        for (; l >= 3 && !pt; l -= 2)
-            if ((rc2 = timed_launch(ln, [&] {
-                     launch_resolve2(sv, N(l - 1), N(l), N(l + 1), ln.counts[l - 1], ln.counts[l], ln.counts[l + 1], ln.st);
-                 }, stt.resolve_ms, stt.resolve_launches)))
-                return rc2;
-        if (l == 2 && !pt &&
-            (rc2 = timed_launch(ln, [&] { launch_resolve(sv, N(2), N(3), ln.counts[2], ln.counts[3], ln.st); },
-                                stt.resolve_ms, stt.resolve_launches)))
-            return rc2;
-        const int before = tg.have + (ps.s0 - tg.s0), mode = (cam->num_samples == 1) ? 2 : (before == 0 ? 1 : 0);   // before: samples already summed
-        const NodeRec* level1 = level >= 1 ? N(1) : nullptr;
-        const NodeRec* level2 = level >= 2 ? N(2) : nullptr;
-        if ((rc2 = timed_launch(ln, [&] {
-                 // (the path tracer: the pass's sample radiance, PtRad)
-                 launch_accumulate(sv, pt ? ln.prad.as<NodeRec>() : N(0), level1, !pt && level >= 1, tg.acc, ps,
-                                   cam->nx, mode, ln.st, !pt,
-                                   ln.counts[0], level >= 1 ? ln.counts[1] : 0, pt ? nullptr : level2,
-                                   level >= 2 ? ln.counts[2] : 0, tg.mom, before);
-             }, stt.accumulate_ms, stt.accumulate_launches)))
-            return rc2;
-        stt.passes++;
-        ln.busy = false;
-        return RTG_OK;
-    };
-    std::deque<int> waiting;           // lanes with a level in flight, in enqueue order
-    // next lane to service: the first (in enqueue order) whose count read-back has landed, so a
-    // lane with a long level does not hold up the others (head-of-line blocking)
-    auto next_ready = [&](int& pick) -> int {
-        for (;;) {
-            for (size_t i = 0; i < waiting.size(); i++) {
-                const hipError_t q = hipEventQuery(s->lanes[waiting[i]].ev_count);
-                if (q == hipSuccess) { pick = (int)i; return RTG_OK; }
-                if (q != hipErrorNotReady) HIP_TRY(q);
-            }
-            if (waiting.size() == 1) { pick = 0; return RTG_OK; }
-            std::this_thread::yield();
-        }
-    };
-    // ------------------------------------------------------------ stream schedule
-    // (round 4).  On the pass schedule every level of every pass is its own launch
-    // (C5: ~22 passes x ~31 levels, the deep levels a few thousand rays each, each behind a host
-    // count read-back; an N=8 dragon shard: the passes holding the glass sphere run their seven
-    // levels alone at the end).  Here each lane runs steps of at most R rays: the survivors of its
-    // previous step -- children of any level, each carrying its slot and level (the path tracer: its
-    // path record too) -- followed by new camera samples from the frame's slot cursor.  A lane runs
-    // a sample's ray tree in consecutive steps of one stream, so every per-sample sum keeps its
-    // order and the frame is bit-identical to the pass schedule (and to the oracle):
-    //  * path tracer: each queued ray carries its sample's running radiance (PtRad); k_pt_shade
-    //    and the per-light k_shadow launches add each vertex's terms in level order, and the
-    //    radiance of a segment of pixels lives in one buffer (16 B per slot, segments sized to an
-    //    eighth of the device memory) and is summed per pixel in sample order (MultiSample,
-    //    src/Scene.cpp:386-411) once the segment's paths have ended;
-    //  * reference integrator: a step's node records [survivors | new samples] stay in HBM; a node's
-    //    children are survivors of the lane's next step (their queue index is their node index
-    //    there).  When a segment's trees have all ended, each lane evaluates RecursiveShading
-    //    bottom-up (src/Scene.cpp:148-219), last step first, and sums the new samples of each step
-    //    per pixel (their level-0 nodes resolved inside the sum).  New samples come in whole pixels;
-    //    a segment closes (no new samples until its trees end) when its node records reach a quarter
-    //    of the device memory.
-    if (o.schedule < RTG_SCHEDULE_AUTO || o.schedule > RTG_SCHEDULE_STREAM) return fail(RTG_ERR_INVALID, "schedule");
-    const bool want_stream = o.schedule == RTG_SCHEDULE_STREAM ||
-                             (o.schedule == RTG_SCHEDULE_AUTO && pt);
-    const bool stream = want_stream && npix > 0 && (long long)npix * total < (1LL << 31) &&
-                        true;
-    if (stream) {
-        const int SL = o.streams > 0 ? std::min(o.streams, 8) : s->stream_lanes;
-        while ((int)s->lanes.size() < SL) {
-            s->lanes.emplace_back();
-            if ((rc = s->lanes.back().create())) { s->lanes.back().destroy(); s->lanes.pop_back(); return rc; }
-        }
-        // rays per step: an even share of the frame, about s->stream_div new-sample steps per lane,
-        // within the memory cap of a pass
-        const long long kR = rtg_pass_rays(nL, pt ? 1 : 0, SL, (uint64_t)dev_total_b);
-        const long long share = (frame_rays + (long long)SL * s->stream_div - 1) / ((long long)SL * s->stream_div);
-        const long long R = o.max_batch_rays > 0 ? std::max<long long>(64, o.max_batch_rays)
-                                                 : std::max<long long>(std::min<long long>(kR, 1LL << 16),
-                                                                       std::min(kR, share));
-        const long long rad_slots = std::max<long long>(total, (long long)(dev_total_b ? dev_total_b / 8 / 16 : 1LL << 28));
-        int seg_np = pt ? (int)std::max<long long>(1, std::min<long long>(npix, rad_slots / total)) : npix;
-        if (pt && o.segment_pixels > 0) seg_np = std::min(seg_np, o.segment_pixels);
-        if (pt && (rc = s->d_rad.grow((size_t)16 * (size_t)seg_np * total))) return rc;
-        const double node_budget = o.segment_nodes > 0 ? (double)sizeof(NodeRec) * o.segment_nodes
-                                                       : (dev_total_b ? 0.25 * (double)dev_total_b : 16e9);
-        const int nLb = std::max(nL, 1);
-        for (int k = 0; k < SL; k++) {
-            Lane& ln = s->lanes[k];
-            if ((int)ln.levels.size() < 3) ln.levels.resize(3);
-            if (pt)
-                for (int b2 = 0; b2 < 2; b2++) {
-                    Level& Q = ln.levels[b2];
-                    if ((rc = Q.rays.grow(kRayBytes * (size_t)R)) || (rc = Q.meta.grow(sizeof(int) * (size_t)R)) ||
-                        (rc = Q.lv.grow((size_t)R)) || (rc = Q.paths.grow(sizeof(PathRec) * (size_t)R)) ||
-                        (rc = Q.carry.grow(kCarryBytes * (size_t)R)))
-                        return rc;
-                    Q.rcap = R;
-                }
-            if ((rc = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc;
-            if (pt && (rc = ln.lcnt.grow(sizeof(unsigned) * 2 * (size_t)nLb))) return rc;
-            HIP_TRY(hipStreamWaitEvent(ln.st, e0, 0));
-        }
-        PassDevA F;
-        F.s0 = tg.s0; F.ns = total; F.p0 = 0; F.npass = npix;
-        F.row_offset = off; F.row_stride = stride; F.rows_owned = rows_owned; F.row_block = block;
-        F.tile_h = tile_h; F.active = tg.active;
-        F.tile_s = tile_s; F.ord_m = tg.ord_m; F.ord_n = tg.ord_n;
-        long long cursor = 0, seg_end = 0, seg_slots = 0;
-        double seg_node_bytes = 0.0;
-        bool seg_closed = false;
-        // one step of lane ln: its m survivors (queued by its previous step) + g new samples
-        auto enqueue_step = [&](Lane& ln, int m, int g) -> int {
-            const int n = m + g;
-            const int gbase = (int)cursor;
-            cursor += g;
-            if (g > 0) ln.sdrain = 0; else ln.sdrain++;
-            stt.max_level = std::max(stt.max_level, ln.sdrain);
-            stt.primary_rays += (uint64_t)g;
-            ln.sq = m; ln.sn = n;
-            const int step = ln.level;
-            Level& A = ln.levels[step & 1];          // this step's queue (survivors)
-            Level& B = ln.levels[(step + 1) & 1];    // the next step's
-            Level& W = pt ? A : ln.levels[2];        // hits / shadow records / lists of the step
-            int rc2;
-            if ((rc2 = W.hits.grow(std::max(sizeof(HitRec), kHitBytes) * (size_t)n)) ||
-                (rc2 = W.shadows.grow(sizeof(ShadowRec) * (size_t)n * nLb)) ||
-                (rc2 = W.slist.grow(sizeof(int) * (size_t)n * nLb)))
-                return rc2;
-            DBuf* nodes = &A.nodes;
-            if (!pt) {                               // the step's node records stay until the resolve
-                if ((int)ln.snodes.size() <= step) ln.snodes.resize(step + 1);
-                if ((int)ln.step_m.size() <= step) { ln.step_m.resize(step + 1); ln.step_g.resize(step + 1); ln.step_gb.resize(step + 1); }
-                nodes = &ln.snodes[step];
-                ln.step_m[step] = m; ln.step_g[step] = g; ln.step_gb[step] = gbase;
-                // children: at most two per ray (DielectricRefraction, src/Scene.cpp:166-209)
-                // (B is free: its rays were the previous step's queue, consumed earlier on this stream)
-                const long long cap = 2LL * std::max(n, 1);
-                if (B.rcap < cap) B.rcap = cap + cap / 4;        // the planes' stride
-                if ((rc2 = B.rays.grow(kRayBytes * (size_t)B.rcap)) || (rc2 = B.lv.grow((size_t)B.rcap)) ||
-                    (!sv.meta_free && (rc2 = B.meta.grow(sizeof(RayMeta) * (size_t)B.rcap))))
-                    return rc2;
-                seg_node_bytes += (double)sizeof(NodeRec) * n;
-                if (seg_node_bytes > node_budget) seg_closed = true;
-            } else {
-                if ((rc2 = A.nodes.grow(sizeof(NodeRec) * (size_t)n))) return rc2;
-            }
-            if ((rc2 = nodes->grow(sizeof(NodeRec) * (size_t)n))) return rc2;
-            const RayQ cur_q = ray_planes(A.rays.p, A.rcap, sv.has_blur);
-            const RayQ next_q = ray_planes(B.rays.p, B.rcap, sv.has_blur);
-            unsigned long long* qc = ln.qcnt.as<unsigned long long>() + (step & 1);
-            HIP_TRY(hipMemsetAsync(qc, 0, sizeof(unsigned long long), ln.st));
-            // the path tracer's radiance (PtRad): survivors' sums in A, their children's in B, a
-            // sample's last vertex writes the segment's rad; per-light list counts of the step
-            PtRad pr{};
-            if (pt) {
-                pr = PtRad{A.carry.as<float4>(), B.carry.as<float4>(), s->d_rad.as<float4>(),
-                           ln.lcnt.as<unsigned>() + (size_t)(step & 1) * nLb};
-                HIP_TRY(hipMemsetAsync(pr.lcnt, 0, sizeof(unsigned) * nLb, ln.st));
-            }
-            if (timing) HIP_TRY(hipEventRecord(ln.ev_t[0], ln.st));
-            launch_trace(sv, cur_q, W.hits.as<HitRec>(), n, exhaustive, sctr, ln.st, g > 0 ? &cd : nullptr, &F, o.seed,
-                         /*compact=*/true, m, gbase);
-            if (timing) HIP_TRY(hipEventRecord(ln.ev_t[1], ln.st));
-            if (pt)
-                launch_pt_shade(sv, cd, 0, F, o.seed, cur_q, A.meta.as<RayMeta>(), W.hits.as<HitRec>(), A.paths.as<PathRec>(),
-                                nodes->as<NodeRec>(), W.shadows.as<ShadowRec>(), W.slist.as<int>(), next_q,
-                                B.meta.as<RayMeta>(), B.paths.as<PathRec>(), qc, n, ln.st, g > 0, m, gbase,
-                                A.lv.as<unsigned char>(), B.lv.as<unsigned char>(), pr, sctr);
-            else
-                launch_shade(sv, cd, 0, F, o.seed, cur_q, A.meta.as<RayMeta>(), W.hits.as<HitRec>(), nodes->as<NodeRec>(),
-                             W.shadows.as<ShadowRec>(), W.slist.as<int>(), next_q, B.meta.as<RayMeta>(), qc, n, ln.st, g > 0 ? 1 : 0, m, gbase, A.lv.as<unsigned char>(), B.lv.as<unsigned char>());
-            if (timing) HIP_TRY(hipEventRecord(ln.ev_t[2], ln.st));
-            HIP_TRY(hipMemcpyAsync(ln.h_count, qc, sizeof(unsigned long long), hipMemcpyDeviceToHost, ln.st));
-            HIP_TRY(hipEventRecord(ln.ev_count, ln.st));
-            if (timing) HIP_TRY(hipEventRecord(ln.ev_t[3], ln.st));
-            // the step's new camera samples: nodes [m, n) (uni_from); the path tracer: one launch per
-            // light, in light order, adding each vertex's T (x) v to its sample's radiance (PtRad)
-            if (pt)
-                launch_pt_shadow(sv, W.shadows.as<ShadowRec>(), W.slist.as<int>(), nodes->as<NodeRec>(), n, exhaustive,
-                                 sctr, d_cnt, ln.st, /*uni_from=*/g > 0 ? m : INT_MAX, pr);
-            else
-                launch_shadow(sv, W.shadows.as<ShadowRec>(), W.slist.as<int>(), reinterpret_cast<const unsigned*>(qc) + 1,
-                              nodes->as<NodeRec>(), n, exhaustive, sctr, d_cnt, ln.st, /*whitted=*/true,
-                              /*uni_from=*/g > 0 ? m : INT_MAX);
-            if (timing) HIP_TRY(hipEventRecord(ln.ev_t[4], ln.st));
-            HIP_TRY(hipGetLastError());
-            ln.level++;
-            ln.busy = true;
-            return RTG_OK;
-        };
-        // new samples for a lane's next step: up to R rays with its survivors, whole pixels on the
-        // reference integrator (a pixel's samples are summed from one step's nodes)
-        auto new_samples = [&](long long m) -> int {
-            const long long left = seg_end - cursor;
-            if (left <= 0 || seg_closed) return 0;
-            long long g = std::min(left, std::max(0LL, R - m));
-            if (!pt) {
-                g = (g / total) * total;
-                if (g == 0 && m == 0) g = std::min<long long>(left, total);
-            }
-            return (int)g;
-        };
-        const long long all_slots = (long long)npix * total;
-        while (cursor < all_slots) {
-            // one segment: [cursor, seg_end) of the slots (the path tracer: a radiance buffer's worth)
-            const long long seg_begin = cursor;
-            if (pt) {
-                F.p0 = (int)(cursor / total);
-                F.npass = std::min(seg_np, npix - F.p0);
-                seg_slots = (long long)F.npass * total;
-                seg_end = cursor + seg_slots;
-                cursor = 0;                          // path tracer slots are segment-relative
-                seg_end = seg_slots;
-            } else {
-                seg_end = all_slots;
-            }
-            seg_node_bytes = 0.0;
-            seg_closed = false;
-            for (int k = 0; k < SL; k++) {
-                Lane& ln = s->lanes[k];
-                ln.level = 0; ln.sdrain = 0; ln.busy = false;
-                const int g = new_samples(0);
-                if (g <= 0) continue;
-                if ((rc = enqueue_step(ln, 0, g))) return rc;
-                waiting.push_back(k);
-            }
-            while (!waiting.empty()) {
-                int pick = 0;
-                if ((rc = next_ready(pick))) return rc;
-                const int k = waiting[pick];
-                waiting.erase(waiting.begin() + pick);
-                Lane& ln = s->lanes[k];
-                HIP_TRY(hipEventSynchronize(ln.ev_count));
-                const unsigned long long q = *ln.h_count;
-                const unsigned next = (unsigned)q;
-                shadow_listed += q >> 32;
-                if (timing) {
-                    float a = 0.0f, b = 0.0f, c = 0.0f;
-                    HIP_TRY(hipEventElapsedTime(&a, ln.ev_t[0], ln.ev_t[1]));
-                    HIP_TRY(hipEventElapsedTime(&c, ln.ev_t[1], ln.ev_t[2]));
-                    HIP_TRY(hipEventSynchronize(ln.ev_t[4]));
-                    HIP_TRY(hipEventElapsedTime(&b, ln.ev_t[3], ln.ev_t[4]));
-                    stt.trace_ms += a; stt.trace_launches++;
-                    stt.shade_ms += c; stt.shade_launches++;
-                    if (nL > 0) { stt.shadow_ms += b; stt.shadow_launches++; }
-                }
-                if ((long long)next > (pt ? 1LL : 2LL) * ln.sn) return fail(RTG_ERR_HIP, "stream queue overflow");
-                if (!pt && next > 0 && ln.level >= (1 << 20)) return fail(RTG_ERR_UNSUPPORTED, "stream: too many steps");
-                stt.secondary_rays += next;
-                const int g = new_samples(next);
-                if ((long long)next + g > 0) {
-                    if ((rc = enqueue_step(ln, (int)next, g))) return rc;
-                    waiting.push_back(k);
-                } else {
-                    ln.busy = false;
-                }
-            }
-            const int mode = cam->num_samples == 1 ? 2 : (tg.have == 0 ? 1 : 0);
-            if (pt) {
-                // the segment's paths have ended: sum every pixel's samples in order, on lane 0 once
-                // every lane's last gather is done; the next segment's gathers wait for that sum
-                Lane& l0 = s->lanes[0];
-                for (int k = 1; k < SL; k++) {
-                    HIP_TRY(hipEventRecord(s->lanes[k].ev_join, s->lanes[k].st));
-                    HIP_TRY(hipStreamWaitEvent(l0.st, s->lanes[k].ev_join, 0));
-                }
-                if ((rc = timed_launch(l0, [&] {
-                         launch_accumulate(sv, s->d_rad.as<NodeRec>(), nullptr, false, tg.acc, F, cam->nx,
-                                           mode, l0.st, /*whitted=*/false, (int)seg_slots, 0, nullptr, 0, tg.mom, tg.have);
-                     }, stt.accumulate_ms, stt.accumulate_launches)))
-                    return rc;
-                HIP_TRY(hipEventRecord(l0.ev_join, l0.st));
-                for (int k = 1; k < SL; k++) HIP_TRY(hipStreamWaitEvent(s->lanes[k].st, l0.ev_join, 0));
-                cursor = (long long)(F.p0 + F.npass) * total;       // back to frame slots
-            } else {
-                // every tree of the segment has ended: bottom-up, last step first, per lane
-                for (int k = 0; k < SL; k++) {
-                    Lane& ln = s->lanes[k];
-                    const int K = ln.level;
-                    for (int j = K - 1; j >= 0; j--) {
-                        const int n = ln.step_m[j] + ln.step_g[j];
-                        const NodePlanes self = node_planes(ln.snodes[j].as<NodeRec>(), n);
-                        const NodePlanes child = j + 1 < K ? node_planes(ln.snodes[j + 1].as<NodeRec>(),
-                                                                         ln.step_m[j + 1] + ln.step_g[j + 1])
-                                                           : self;     // no children: every link is -1
-                        if (ln.step_m[j] > 0 &&
-                            (rc = timed_launch(ln, [&] { launch_resolve_planes(sv, self, child, ln.step_m[j], ln.st); },
-                                               stt.resolve_ms, stt.resolve_launches)))
-                            return rc;
-                        if (ln.step_g[j] > 0) {
-                            const int mj = ln.step_m[j];
-                            const NodePlanes l0 = {self.col + mj, self.pnt + mj, self.link + mj};
-                            PassDevA P = F;
-                            P.p0 = ln.step_gb[j] / total;
-                            P.npass = ln.step_g[j] / total;
-                            if ((rc = timed_launch(ln, [&] {
-                                     launch_accumulate_planes(sv, l0, child, true, tg.acc, P, cam->nx, mode,
-                                                              ln.st, tg.mom, tg.have);
-                                 }, stt.accumulate_ms, stt.accumulate_launches)))
-                                return rc;
-                        }
-                    }
-                    HIP_TRY(hipGetLastError());
-                }
-                if (cursor == seg_begin) return fail(RTG_ERR_OOM, "stream: a segment made no progress");
-            }
-            stt.passes++;
-        }
-    }
-    for (int k = 0; k < L && !stream; k++)
-        if (!s->lanes[k].passes.empty() && npix > 0) {
+    int rc;
+    for (int k = 0; k < lanes; k++)
+        if (!s->lanes[k].passes.empty()) {
             if ((rc = start_pass(s->lanes[k]))) return rc;
             waiting.push_back(k);
         }
     while (!waiting.empty()) {
-        int pick = 0;
-        if ((rc = next_ready(pick))) return rc;
-        const int k = waiting[pick];
-        waiting.erase(waiting.begin() + pick);
+        int k;
+        unsigned next;
+        if ((rc = drain(k, next))) return rc;
         Lane& ln = s->lanes[k];
-        HIP_TRY(hipEventSynchronize(ln.ev_count));
-        const unsigned long long q = *ln.h_count;
-        const unsigned next = (unsigned)q;
-        shadow_listed += q >> 32;
-        if (timing) {
-            float a = 0.0f, b = 0.0f, c = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&a, ln.ev_t[0], ln.ev_t[1]));
-            HIP_TRY(hipEventElapsedTime(&c, ln.ev_t[1], ln.ev_t[2]));
-            stt.trace_ms += a;
-            stt.trace_launches++;
-            stt.shade_ms += c;
-            stt.shade_launches++;
-            if (nL > 0) {
-                HIP_TRY(hipEventSynchronize(ln.ev_t[4]));   // the count arrives before the shadow pass ends
-                HIP_TRY(hipEventElapsedTime(&b, ln.ev_t[3], ln.ev_t[4]));
-                stt.shadow_ms += b;
-                stt.shadow_launches++;
-            }
-        }
         const int n = ln.counts[ln.level];
         const bool may_spawn = ln.level + 1 < max_levels;
         const size_t cap = may_spawn ? 2 * (size_t)n : 1;
@@ -3073,7 +2855,7 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             ln.counts.push_back((int)next);
             stt.secondary_rays += next;
             ln.level++;
-            if ((rc = enqueue_level(ln))) return rc;
+            if ((rc = level_step(ln))) return rc;
             waiting.push_back(k);
             continue;
         }
@@ -3083,24 +2865,218 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             waiting.push_back(k);
         }
     }
-    for (int k = 0; k < (int)s->lanes.size(); k++) {
-        HIP_TRY(hipEventRecord(ejoin, s->lanes[k].st));
-        HIP_TRY(hipStreamWaitEvent(st, ejoin, 0));
+    return RTG_OK;
+}
+
+// ------------------------------------------------------------ stream schedule
+// (round 4).  On the pass schedule every level of every pass is its own launch
+// (C5: ~22 passes x ~31 levels, the deep levels a few thousand rays each, each behind a host
+// count read-back; an N=8 dragon shard: the passes holding the glass sphere run their seven
+// levels alone at the end).  Here each lane runs steps of at most R rays: the survivors of its
+// previous step -- children of any level, each carrying its slot and level (the path tracer: its
+// path record too) -- followed by new camera samples from the frame's slot cursor.  A lane runs
+// a sample's ray tree in consecutive steps of one stream, so every per-sample sum keeps its
+// order and the frame is bit-identical to the pass schedule (and to the oracle):
+//  * path tracer: each queued ray carries its sample's running radiance (PtRad); k_pt_shade
+//    and the per-light k_shadow launches add each vertex's terms in level order, and the
+//    radiance of a segment of pixels lives in one buffer (16 B per slot, segments sized to an
+//    eighth of the device memory) and is summed per pixel in sample order (MultiSample,
+//    src/Scene.cpp:386-411) once the segment's paths have ended;
+//  * reference integrator: a step's node records [survivors | new samples] stay in HBM; a node's
+//    children are survivors of the lane's next step (their queue index is their node index
+//    there).  When a segment's trees have all ended, each lane evaluates RecursiveShading
+//    bottom-up (src/Scene.cpp:148-219), last step first, and sums the new samples of each step
+//    per pixel (their level-0 nodes resolved inside the sum).  New samples come in whole pixels;
+//    a segment closes (no new samples until its trees end) when its node records reach a quarter
+//    of the device memory.
+// one step of lane ln: its m survivors (queued by its previous step) + g new samples
+int Render::stream_step(Lane& ln, int m, int g) {
+    const int n = m + g;
+    const int nLb = std::max(nL, 1);
+    const int gbase = (int)seg.cursor;
+    seg.cursor += g;
+    if (g > 0) ln.sdrain = 0; else ln.sdrain++;
+    stt.max_level = std::max(stt.max_level, ln.sdrain);
+    stt.primary_rays += (uint64_t)g;
+    ln.sn = n;
+    const int step_i = ln.level;
+    Level& A = ln.levels[step_i & 1];          // this step's queue (survivors)
+    Level& B = ln.levels[(step_i + 1) & 1];    // the next step's
+    Level& W = pt ? A : ln.levels[2];          // hits / shadow records / lists of the step
+    int rc;
+    if ((rc = W.hits.grow(std::max(sizeof(HitRec), kHitBytes) * (size_t)n)) ||
+        (rc = W.shadows.grow(sizeof(ShadowRec) * (size_t)n * nLb)) ||
+        (rc = W.slist.grow(sizeof(int) * (size_t)n * nLb)))
+        return rc;
+    DBuf* nodes = &A.nodes;
+    if (!pt) {                               // the step's node records stay until the resolve
+        if ((int)ln.snodes.size() <= step_i) ln.snodes.resize(step_i + 1);
+        if ((int)ln.step_m.size() <= step_i) { ln.step_m.resize(step_i + 1); ln.step_g.resize(step_i + 1); ln.step_gb.resize(step_i + 1); }
+        nodes = &ln.snodes[step_i];
+        ln.step_m[step_i] = m; ln.step_g[step_i] = g; ln.step_gb[step_i] = gbase;
+        // children: at most two per ray (DielectricRefraction, src/Scene.cpp:166-209)
+        // (B is free: its rays were the previous step's queue, consumed earlier on this stream)
+        const long long cap = 2LL * std::max(n, 1);
+        if (B.rcap < cap) B.rcap = cap + cap / 4;        // the planes' stride
+        if ((rc = B.rays.grow(kRayBytes * (size_t)B.rcap)) || (rc = B.lv.grow((size_t)B.rcap)) ||
+            (!sv.meta_free && (rc = B.meta.grow(sizeof(RayMeta) * (size_t)B.rcap))))
+            return rc;
+        seg.node_bytes += (double)sizeof(NodeRec) * n;
+        if (seg.node_bytes > node_budget) seg.closed = true;
+    } else {
+        if ((rc = A.nodes.grow(sizeof(NodeRec) * (size_t)n))) return rc;
     }
-    // (no out_dev: a frame, which resolves on request -- rtg_frame_resolve*)
-    if (out_dev && o.compact_rows)
-        launch_finalize(tg.acc, out_dev, cam->nx, rows_owned, 0, 1, 1, total, st);
-    else if (out_dev)
-        launch_finalize(tg.acc, out_dev, cam->nx, cam->ny, off, stride, block, total, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    unsigned nan_queries = 0;
-    Counters ctr{};
-    HIP_TRY(hipMemcpy(&nan_queries, d_cnt, sizeof(unsigned), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&ctr, d_stats, sizeof(Counters), hipMemcpyDeviceToHost));
+    if ((rc = nodes->grow(sizeof(NodeRec) * (size_t)n))) return rc;
+    StepIO io{};
+    io.rays = ray_planes(A.rays.p, A.rcap, sv.has_blur);
+    io.meta = A.meta.as<RayMeta>(); io.hits = W.hits.as<HitRec>(); io.paths = A.paths.as<PathRec>();
+    io.nodes = nodes->as<NodeRec>(); io.shadows = W.shadows.as<ShadowRec>(); io.slist = W.slist.as<int>();
+    io.next_rays = ray_planes(B.rays.p, B.rcap, sv.has_blur);
+    io.next_meta = B.meta.as<RayMeta>(); io.next_paths = B.paths.as<PathRec>();
+    io.qcount = ln.qcnt.as<unsigned long long>() + (step_i & 1);
+    HIP_TRY(hipMemsetAsync(io.qcount, 0, sizeof(unsigned long long), ln.st));
+    io.n = n; io.nq = m; io.gbase = gbase; io.gen = g > 0;
+    io.lv_in = A.lv.as<unsigned char>(); io.lv_out = B.lv.as<unsigned char>();
+    // the path tracer's radiance (PtRad): survivors' sums in A, their children's in B, a
+    // sample's last vertex writes the segment's rad; per-light list counts of the step
+    if (pt) {
+        io.pr = PtRad{A.carry.as<float4>(), B.carry.as<float4>(), s->d_rad.as<float4>(),
+                      ln.lcnt.as<unsigned>() + (size_t)(step_i & 1) * nLb};
+        HIP_TRY(hipMemsetAsync(io.pr.lcnt, 0, sizeof(unsigned) * nLb, ln.st));
+    }
+    // the step's new camera samples: nodes [m, n) (the wave-uniform shadow walk)
+    io.uni_from = g > 0 ? m : INT_MAX;
+    ln.level++;
+    return step(ln, seg.F, io);
+}
+
+// new samples for a lane's next step: up to R rays with its survivors, whole pixels on the
+// reference integrator (a pixel's samples are summed from one step's nodes)
+int Render::new_samples(long long m) const {
+    const long long left = seg.end - seg.cursor;
+    if (left <= 0 || seg.closed) return 0;
+    long long g = std::min(left, std::max(0LL, R - m));
+    if (!pt) {
+        g = (g / total) * total;
+        if (g == 0 && m == 0) g = std::min<long long>(left, total);
+    }
+    return (int)g;
+}
+
+int Render::run_stream() {
+    int rc;
+    const int nLb = std::max(nL, 1);
+    if (pt && (rc = s->d_rad.grow((size_t)16 * (size_t)seg_np * total))) return rc;
+    for (int k = 0; k < lanes; k++) {
+        Lane& ln = s->lanes[k];
+        if ((int)ln.levels.size() < 3) ln.levels.resize(3);
+        if (pt)
+            for (int b2 = 0; b2 < 2; b2++) {
+                Level& Q = ln.levels[b2];
+                if ((rc = Q.rays.grow(kRayBytes * (size_t)R)) || (rc = Q.meta.grow(sizeof(int) * (size_t)R)) ||
+                    (rc = Q.lv.grow((size_t)R)) || (rc = Q.paths.grow(sizeof(PathRec) * (size_t)R)) ||
+                    (rc = Q.carry.grow(kCarryBytes * (size_t)R)))
+                    return rc;
+                Q.rcap = R;
+            }
+        if ((rc = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc;
+        if (pt && (rc = ln.lcnt.grow(sizeof(unsigned) * 2 * (size_t)nLb))) return rc;
+    }
+    PassDevA& F = seg.F;
+    F = order;
+    F.s0 = tg.s0; F.ns = total; F.p0 = 0; F.npass = npix;
+    const long long all_slots = (long long)npix * total;
+    while (seg.cursor < all_slots) {
+        // one segment: [cursor, end) of the slots (the path tracer: a radiance buffer's worth)
+        const long long seg_begin = seg.cursor;
+        if (pt) {
+            F.p0 = (int)(seg.cursor / total);
+            F.npass = std::min(seg_np, npix - F.p0);
+            seg.slots = (long long)F.npass * total;
+            seg.cursor = 0;                          // path tracer slots are segment-relative
+            seg.end = seg.slots;
+        } else {
+            seg.end = all_slots;
+        }
+        seg.node_bytes = 0.0;
+        seg.closed = false;
+        for (int k = 0; k < lanes; k++) {
+            Lane& ln = s->lanes[k];
+            ln.level = 0; ln.sdrain = 0;
+            const int g = new_samples(0);
+            if (g <= 0) continue;
+            if ((rc = stream_step(ln, 0, g))) return rc;
+            waiting.push_back(k);
+        }
+        while (!waiting.empty()) {
+            int k;
+            unsigned next;
+            if ((rc = drain(k, next))) return rc;
+            Lane& ln = s->lanes[k];
+            if ((long long)next > (pt ? 1LL : 2LL) * ln.sn) return fail(RTG_ERR_HIP, "stream queue overflow");
+            if (!pt && next > 0 && ln.level >= (1 << 20)) return fail(RTG_ERR_UNSUPPORTED, "stream: too many steps");
+            stt.secondary_rays += next;
+            const int g = new_samples(next);
+            if ((long long)next + g > 0) {
+                if ((rc = stream_step(ln, (int)next, g))) return rc;
+                waiting.push_back(k);
+            }
+        }
+        const int mode = cam->num_samples == 1 ? 2 : (tg.have == 0 ? 1 : 0);
+        if (pt) {
+            // the segment's paths have ended: sum every pixel's samples in order, on lane 0 once
+            // every lane's last gather is done; the next segment's gathers wait for that sum
+            Lane& l0 = s->lanes[0];
+            for (int k = 1; k < lanes; k++) {
+                HIP_TRY(hipEventRecord(s->lanes[k].ev_join, s->lanes[k].st));
+                HIP_TRY(hipStreamWaitEvent(l0.st, s->lanes[k].ev_join, 0));
+            }
+            if ((rc = timed_launch(l0, [&] {
+                     launch_accumulate(sv, s->d_rad.as<NodeRec>(), nullptr, false, tg.acc, F, cam->nx,
+                                       mode, l0.st, /*whitted=*/false, (int)seg.slots, 0, nullptr, 0, tg.mom, tg.have);
+                 }, stt.accumulate_ms, stt.accumulate_launches)))
+                return rc;
+            HIP_TRY(hipEventRecord(l0.ev_join, l0.st));
+            for (int k = 1; k < lanes; k++) HIP_TRY(hipStreamWaitEvent(s->lanes[k].st, l0.ev_join, 0));
+            seg.cursor = (long long)(F.p0 + F.npass) * total;       // back to frame slots
+        } else {
+            // every tree of the segment has ended: bottom-up, last step first, per lane
+            for (int k = 0; k < lanes; k++) {
+                Lane& ln = s->lanes[k];
+                const int K = ln.level;
+                for (int j = K - 1; j >= 0; j--) {
+                    const int n = ln.step_m[j] + ln.step_g[j];
+                    const NodePlanes self = node_planes(ln.snodes[j].as<NodeRec>(), n);
+                    const NodePlanes child = j + 1 < K ? node_planes(ln.snodes[j + 1].as<NodeRec>(),
+                                                                     ln.step_m[j + 1] + ln.step_g[j + 1])
+                                                       : self;     // no children: every link is -1
+                    if (ln.step_m[j] > 0 &&
+                        (rc = timed_launch(ln, [&] { launch_resolve_planes(sv, self, child, ln.step_m[j], ln.st); },
+                                           stt.resolve_ms, stt.resolve_launches)))
+                        return rc;
+                    if (ln.step_g[j] > 0) {
+                        const int mj = ln.step_m[j];
+                        const NodePlanes l0 = {self.col + mj, self.pnt + mj, self.link + mj};
+                        PassDevA P = F;
+                        P.p0 = ln.step_gb[j] / total;
+                        P.npass = ln.step_g[j] / total;
+                        if ((rc = timed_launch(ln, [&] {
+                                 launch_accumulate_planes(sv, l0, child, true, tg.acc, P, cam->nx, mode,
+                                                          ln.st, tg.mom, tg.have);
+                             }, stt.accumulate_ms, stt.accumulate_launches)))
+                            return rc;
+                    }
+                }
+                HIP_TRY(hipGetLastError());
+            }
+            if (seg.cursor == seg_begin) return fail(RTG_ERR_OOM, "stream: a segment made no progress");
+        }
+        stt.passes++;
+    }
+    return RTG_OK;
+}
+
+void Render::fill_stats(float ms, unsigned nan_queries, const Counters& ctr) {
     stt.shadow_rays = shadow_listed - nan_queries;
     stt.total_rays = stt.primary_rays + stt.secondary_rays + stt.shadow_rays;
     stt.render_ms = ms;
@@ -3140,10 +3116,55 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     }
     stt.devices = 1;
     s->stats = stt;
-    return RTG_OK;
 }
 
-}  // extern "C"
+}  // namespace
+
+static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, float* out_dev,
+                       hipStream_t st, const RenderTarget* target = nullptr) {
+    Render r(s, cam);
+    int rc;
+    if ((rc = r.plan(opts, target))) return rc;
+    if (!r.tg.acc) { if ((rc = s->d_acc.grow(sizeof(float) * 3 * std::max<size_t>(r.npix, 1)))) return rc; r.tg.acc = s->d_acc.as<float>(); }
+    if ((rc = s->d_counters.grow(sizeof(unsigned) * 64))) return rc;
+    if ((rc = s->d_stats.grow(sizeof(Counters)))) return rc;
+    r.d_cnt = s->d_counters.as<unsigned>();
+    Counters* d_stats = s->d_stats.as<Counters>();
+    r.sctr = r.o.collect_stats ? d_stats : nullptr;
+    HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, sizeof(unsigned) * 64, st));
+    HIP_TRY(hipMemsetAsync(s->d_stats.p, 0, sizeof(Counters), st));
+
+    struct Events {                     // RAII: released on every return path
+        hipEvent_t e[3] = {};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+    hipEvent_t e0 = ev.e[0], e1 = ev.e[1], ejoin = ev.e[2];
+    HIP_TRY(hipEventRecord(e0, st));
+    if ((rc = ensure_lanes(s, r.lanes))) return rc;
+    for (int k = 0; k < r.lanes; k++) HIP_TRY(hipStreamWaitEvent(s->lanes[k].st, e0, 0));
+    if ((rc = r.stream ? r.run_stream() : r.run_passes())) return rc;
+    for (int k = 0; k < (int)s->lanes.size(); k++) {
+        HIP_TRY(hipEventRecord(ejoin, s->lanes[k].st));
+        HIP_TRY(hipStreamWaitEvent(st, ejoin, 0));
+    }
+    // (no out_dev: a frame, which resolves on request -- rtg_frame_resolve*)
+    if (out_dev && r.o.compact_rows)
+        launch_finalize(r.tg.acc, out_dev, cam->nx, r.order.rows_owned, 0, 1, 1, r.total, st);
+    else if (out_dev)
+        launch_finalize(r.tg.acc, out_dev, cam->nx, cam->ny, r.order.row_offset, r.order.row_stride, r.order.row_block, r.total, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    unsigned nan_queries = 0;
+    Counters ctr{};
+    HIP_TRY(hipMemcpy(&nan_queries, r.d_cnt, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&ctr, d_stats, sizeof(Counters), hipMemcpyDeviceToHost));
+    r.fill_stats(ms, nan_queries, ctr);
+    return RTG_OK;
+}
 
 // ------------------------------------------------------------------ hooks for rtg_multi.cpp
 namespace rtg {
@@ -3282,19 +3303,6 @@ static int order_multiplier(int n) {
 }
 constexpr int kOrderMaxSamples = 32768;      // (j * m) stays below 2^31
 
-// The pixel order of the frame's renders: render_impl's rule for tile_h / tile_s, which the active list
-// (tile-order indices) must share.
-static PassDev frame_tiles(const rtg_frame* f) {
-    const rtg_render_opts& o = f->opts;
-    const int stride = o.row_stride > 1 ? o.row_stride : 1, block = o.row_block > 1 ? o.row_block : 1;
-    PassDev ps{};
-    ps.row_offset = o.row_offset; ps.row_stride = stride; ps.rows_owned = f->rows_owned; ps.row_block = block;
-    ps.tile_h = stride > 1 && block < 8 ? (block >= 4 ? 4 : block >= 2 ? 2 : 1) : 8;
-    const int tile_s = o.tile_band > 0 ? std::min(o.tile_band, 1 << 12) : std::max(1, kBandRows / ps.tile_h);
-    ps.tile_s = (int)std::min<long long>(tile_s, ((1LL << 31) - 1) / (8LL * f->cam.nx));
-    return ps;
-}
-
 // First retirement of a frame: the count words (all active) and the list's buffers.
 static int frame_adapt_alloc(rtg_frame* f) {
     if (f->adaptive) return RTG_OK;
@@ -3317,7 +3325,10 @@ static int frame_adapt_alloc(rtg_frame* f) {
 // Rebuild the active list from the count words and read its length back.
 static int frame_rebuild_active(rtg_frame* f) {
     const size_t nb = ((size_t)std::max(f->npix, 1) + kScanBlock - 1) / kScanBlock;
-    launch_active_list(f->cnt.as<unsigned>(), f->npix, frame_tiles(f), f->cam.nx, f->scan.as<int>(), f->active.as<int>(),
+    PassDevA tiles{};                        // the pixel order of the frame's renders: the list holds its indices
+    int rc;
+    if ((rc = pixel_order(f->opts, &f->cam, tiles))) return rc;
+    launch_active_list(f->cnt.as<unsigned>(), f->npix, tiles, f->cam.nx, f->scan.as<int>(), f->active.as<int>(),
                        nullptr);
     HIP_TRY(hipGetLastError());
     int n = 0;
@@ -3769,7 +3780,7 @@ int32_t rtg_trace_closest(rtg_scene* s, const rtg_ray* rays, int32_t n, rtg_hit*
             return rc;
         }
         const RayQ q = ray_planes(dr.p, n, true);
-        launch_trace(s->sv, q, dh.as<HitRec>(), n, traversal == 1, nullptr, nullptr);
+        launch_trace_queued(s->sv, q, dh.as<HitRec>(), n, traversal == 1, nullptr);
         launch_hit_details(s->sv, q, dh.as<HitRec>(), dout.as<rtg_hit>(), s->d_origprim.as<int>(), n, nullptr);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpy(hits, dout.p, sizeof(rtg_hit) * (size_t)n, hipMemcpyDeviceToHost);
@@ -3851,22 +3862,15 @@ int32_t rtg_render_aov(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
         rtg_render_opts o{};
         if (opts) o = *opts;
         if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_UNSUPPORTED, "feature buffers render on the scene's device only");
-        const int stride = o.row_stride > 1 ? o.row_stride : 1, block = o.row_block > 1 ? o.row_block : 1;
-        if (o.row_offset < 0 || o.row_offset >= stride) return fail(RTG_ERR_INVALID, "row_offset out of range");
-        const int rows_owned = rtg_shard_rows(cam->ny, o.row_offset, stride, block);
-        if ((long long)rows_owned * cam->nx > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
-        if ((long long)8 * cam->nx >= (1LL << 31)) return fail(RTG_ERR_UNSUPPORTED, "image wider than 2^28 pixels");
+        o.tile_band = 0;                    // the renders' pixel order with the default band height
+        PassDevA ps{};
+        if ((rc = pixel_order(o, cam, ps))) return rc;
+        ps.s0 = ao.first_sample; ps.ns = window;
         if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
         HIP_TRY(hipSetDevice(s->device));
-        const int npix = rows_owned * cam->nx;
+        const int rows_owned = ps.rows_owned, npix = rows_owned * cam->nx;
         const int out_rows = o.compact_rows ? rows_owned : cam->ny;
         const size_t nout = (size_t)out_rows * cam->nx;
-        // render_impl's pixel order with the default band height
-        PassDev ps{};
-        ps.s0 = ao.first_sample; ps.ns = window;
-        ps.row_offset = o.row_offset; ps.row_stride = stride; ps.rows_owned = rows_owned; ps.row_block = block;
-        ps.tile_h = stride > 1 && block < 8 ? (block >= 4 ? 4 : block >= 2 ? 2 : 1) : 8;
-        ps.tile_s = (int)std::min<long long>(std::max(1, kBandRows / ps.tile_h), ((1LL << 31) - 1) / (8LL * cam->nx));
         const CameraDev cd = make_camera(cam);
 
         struct Scratch {                    // RAII: released on every return path
@@ -3892,10 +3896,7 @@ int32_t rtg_render_aov(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
         if ((long long)window * chunk > (1LL << 31) - 1) return fail(RTG_ERR_UNSUPPORTED, "sample window too long");
         const int npasses = (npix + chunk - 1) / chunk;
         const int L = std::max(1, std::min(4, npasses));
-        while ((int)s->lanes.size() < L) {
-            s->lanes.emplace_back();
-            if ((rc = s->lanes.back().create())) { s->lanes.back().destroy(); s->lanes.pop_back(); return rc; }
-        }
+        if ((rc = ensure_lanes(s, L))) return rc;
         const size_t slots = (size_t)std::min(chunk, std::max(npix, 1)) * window;
         if ((rc = w.rec.grow(kAovRecBytes * slots * L))) return rc;
         for (hipEvent_t& x : w.e) HIP_TRY(hipEventCreate(&x));

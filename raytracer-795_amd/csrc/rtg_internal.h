@@ -431,33 +431,6 @@ struct PtRad {
 constexpr size_t kCarryBytes = 16;    // float4 per queued ray
 
 // Host-side launchers (rtg_device.hip) ------------------------------------------------
-struct LevelBuffers;
-struct PassDevA;      // a pass of an adaptive frame (below)
-// gen_cam / gen_ps non-null: level 0 (either integrator), rays are generated in the kernel
-// nq / gbase (with gen_cam): rays [0, nq) are queued, ray i >= nq is the primary ray of slot gbase + i - nq
-void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive,
-                  Counters* ctr, hipStream_t st, const CameraDev* gen_cam = nullptr, const PassDev* gen_ps = nullptr,
-                  uint64_t seed = 0, bool compact = false, int nq = 0, int gbase = 0);
-// (the PassDevA overloads of the launchers: an adaptive frame's passes; a plain() one takes the PassDev kernels)
-void launch_trace(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive,
-                  Counters* ctr, hipStream_t st, const CameraDev* gen_cam, const PassDevA* gen_ps,
-                  uint64_t seed = 0, bool compact = false, int nq = 0, int gbase = 0);
-// gen: 1 = rays i >= nq are primary rays of slots gbase + i - nq, 0 = queued only, -1 = a pass's level
-// (primaries iff rays.a is null); lv_in / lv_out: per-ray levels of a stream step (or null)
-void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed, const RayQ rays, const RayMeta* meta, const HitRec* hits, NodeRec* nodes,
-                  ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta,
-                  unsigned long long* qcount, int n, hipStream_t st,
-                  int gen = -1, int nq = 0, int gbase = 0, const unsigned char* lv_in = nullptr,
-                  unsigned char* lv_out = nullptr);
-void launch_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed, const RayQ rays,
-                  const RayMeta* meta, const HitRec* hits, NodeRec* nodes, ShadowRec* shadows, int* slist,
-                  const RayQ next_rays, RayMeta* next_meta, unsigned long long* qcount, int n, hipStream_t st,
-                  int gen = -1, int nq = 0, int gbase = 0, const unsigned char* lv_in = nullptr,
-                  unsigned char* lv_out = nullptr);
-// the bottom-up step and the accumulation on explicit node planes (stream schedule: a step's nodes
-// [0, count) against the next step's; the primaries of a pixel range at an offset of a step's planes)
-void launch_resolve_planes(const SceneView& sv, const NodePlanes& self, const NodePlanes& child, int count,
-                           hipStream_t st);
 // Where a render's samples go.  rtg_render*: the scene's accumulator, the camera's whole sample range,
 // nothing accumulated before, no moments (target == nullptr).  A frame (rtg_frame_add_samples): its own
 // accumulator, samples [s0, s0 + ns) of the camera's, behind `have` samples the accumulator already holds.
@@ -485,29 +458,51 @@ struct PassDevA : PassDev {
     bool plain() const { return !active && !ord_m; }
 };
 
+// What one trace -> shade -> shadow step reads and writes: a level of a pass, or a step of the stream
+// schedule (Render::step, rtg_host.cpp).  Each schedule fills it from its own buffers.
+struct StepIO {
+    RayQ rays;                    // queued rays [0, nq) (a pass's level 0: none)
+    const RayMeta* meta;
+    HitRec* hits;
+    PathRec* paths;               // path tracer
+    NodeRec* nodes;
+    ShadowRec* shadows;
+    int* slist;
+    RayQ next_rays;               // the children the step queues, their count in the low word of *qcount (the
+    RayMeta* next_meta;           // high word: the Whitted shadow list's entries)
+    PathRec* next_paths;
+    unsigned long long* qcount;
+    int n;                        // rays of the step
+    int nq, gbase;                // gen: rays [0, nq) are queued, ray i >= nq is the primary ray of slot gbase + i - nq
+    bool gen;                     // the step holds primary rays, generated in the kernels (no level-0 ray buffer)
+    int level;                    // a pass's level; 0 on the stream schedule, whose rays carry theirs:
+    const unsigned char* lv_in;   // per-ray levels of a stream step (or null)
+    unsigned char* lv_out;
+    PtRad pr;                     // path tracer
+    int uni_from;                 // shadow queries: first camera-sample node (wave-uniform walk), INT_MAX none
+};
+void launch_trace(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+                  int exhaustive, Counters* ctr, hipStream_t st);
+// queued rays only, full hit records (rtg_trace_closest): no camera, no pass
+void launch_trace_queued(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, hipStream_t st);
+void launch_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+                  hipStream_t st);
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+                     Counters* ctr, hipStream_t st);
+void launch_shadow(const SceneView& sv, const StepIO& io, int exhaustive, Counters* ctr, unsigned* nan_queries,
+                   hipStream_t st);
+// the path tracer's queries: one launch per light, in light order (PtRad)
+void launch_pt_shadow(const SceneView& sv, const StepIO& io, int exhaustive, Counters* ctr, unsigned* nan_queries,
+                      hipStream_t st);
+// the bottom-up step and the accumulation on explicit node planes (stream schedule: a step's nodes
+// [0, count) against the next step's; the primaries of a pixel range at an offset of a step's planes)
+void launch_resolve_planes(const SceneView& sv, const NodePlanes& self, const NodePlanes& child, int count,
+                           hipStream_t st);
 // mom (a frame's moments, or null): mean and M2 of each pixel's sample luminance (2 floats per owned
 // pixel, in `acc` order), continued over this launch's samples; mom_k0 = samples they already hold
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDev& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
-                              int mom_k0 = 0);
-void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
                               float* acc, const PassDevA& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
                               int mom_k0 = 0);
-void launch_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, const unsigned* scount, NodeRec* nodes,
-                   int n, int exhaustive, Counters* ctr, unsigned* nan_queries, hipStream_t st, bool whitted = true, int uni_from = INT_MAX);  // uni_from: first camera-sample node (wave-uniform walk)
-// the path tracer's queries: one launch per light, in light order (PtRad)
-void launch_pt_shadow(const SceneView& sv, ShadowRec* shadows, const int* slist, NodeRec* nodes, int n, int exhaustive,
-                      Counters* ctr, unsigned* nan_queries, hipStream_t st, int uni_from, const PtRad& pr);
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDev& ps, uint64_t seed,
-                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
-                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
-                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
-                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr = nullptr);
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, int level, const PassDevA& ps, uint64_t seed,
-                     const RayQ rays, const RayMeta* meta, const HitRec* hits, PathRec* paths, NodeRec* nodes,
-                     ShadowRec* shadows, int* slist, const RayQ next_rays, RayMeta* next_meta, PathRec* next_paths,
-                     unsigned long long* qcount, int n, hipStream_t st, bool gen, int nq, int gbase,
-                     const unsigned char* lv_in, unsigned char* lv_out, const PtRad& pr, Counters* ctr = nullptr);
 void launch_resolve(const SceneView& sv, NodeRec* nodes, const NodeRec* child_nodes, int n, int n_child,
                     hipStream_t st);
 // levels p (nodes) and p + 1 (child_nodes, resolved inline, not stored) against the resolved level p + 2
@@ -516,9 +511,6 @@ void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_n
 // mode: 0 = continue the running sum, 1 = start from (0,0,0), 2 = assign (single-sample camera)
 // level0 / level1 hold NodePlanes over n0 / n1 nodes; whitted: resolve level 0 against level 1
 // level2 (optional): level 1 is resolved inline against it (the bottom-up pass left level 1 unresolved)
-void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
-                       const PassDev& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
-                       const NodeRec* level2 = nullptr, int n2 = 0, float* mom = nullptr, int mom_k0 = 0);
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
                        const PassDevA& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
                        const NodeRec* level2 = nullptr, int n2 = 0, float* mom = nullptr, int mom_k0 = 0);

@@ -1,11 +1,12 @@
-"""Pass scheduling of rtg_render (rtg_host.cpp render_impl): pass sizes, lanes and the tile order of
-a pass's pixels (tile_pixel).  Which pass renders a pixel must never change its value -- every
-sample of a pixel is in one pass and summed in sample order (src/Scene.cpp:386-409) -- so every
-schedule gives the same frame bit for bit, repeated frames included."""
+"""Pass scheduling of rtg_render (rtg_host.cpp: Render::plan, run_passes / run_stream over Render::step /
+Render::drain) and a pass's tile order (pixel_order, tile_pixel).  Which pass renders a pixel must never
+change its value -- every sample of a pixel is in one pass and summed in sample order (src/Scene.cpp:386-409)
+-- so every schedule gives the same frame bit for bit, repeated frames included."""
 import numpy as np
 import pytest
 
 import rtg
+from rtg import _abi as A
 from rtg import scenegen
 
 pytestmark = pytest.mark.gpu
@@ -71,3 +72,39 @@ def test_more_shards_than_row_blocks(gpu, ny):
         ref = r.render(0)
         shard = r.render(0, num_devices=3, devices=[0, 0, 0])
     assert np.array_equal(_bits(shard), _bits(ref))
+
+
+@pytest.mark.parametrize("schedule", [A.SCHEDULE_PASSES, A.SCHEDULE_STREAM], ids=["passes", "stream"])
+@pytest.mark.parametrize("make", [lambda: scenegen.dragon1m(40, 24, spp=4, nu=60, nv=30),
+                                  lambda: scenegen.cornell_pt(32, 18, spp=16)], ids=["dragon", "cornell_pt"])
+def test_collect_timing_changes_neither_frame_nor_counts(gpu, make, schedule):
+    """collect_timing puts event pairs round every launch and waits for them (Render::step, Render::drain,
+    timed_launch): the frame's bits and ray counts stay those of the untimed frame, with and without
+    collect_stats, every step is counted once per kernel, and the pass schedule runs the passes of the
+    explicit-batch rule (Render::plan) with one accumulation each.  The dragon (Whitted, glass and mirror)
+    has several levels and both resolve forms, cornell_pt is the path tracer; both have lights."""
+    sc = make()
+    cam = sc.cameras[0]
+    npix, spp, batch = cam.nx * cam.ny, cam.num_samples, 700
+    kw = dict(schedule=schedule, max_batch_rays=batch, streams=2)
+    counts = ("primary_rays", "secondary_rays", "shadow_rays")
+    with rtg.Renderer(sc, device=gpu) as r:
+        ref = r.render(0, **kw)
+        ref_st = r.stats()
+        timed = r.render(0, collect_timing=1, **kw)
+        st = r.stats()
+        both = r.render(0, collect_timing=1, collect_stats=1, **kw)
+        both_st = r.stats()
+    assert np.array_equal(_bits(timed), _bits(ref))
+    assert np.array_equal(_bits(both), _bits(ref))
+    for k in counts:
+        assert st[k] == ref_st[k] and both_st[k] == ref_st[k], k
+    for t in (st, both_st):
+        assert t["trace_launches"] == t["shade_launches"] >= t["passes"] >= 1
+        assert t["shadow_launches"] == t["trace_launches"]
+    if schedule == A.SCHEDULE_PASSES:
+        ns_chunk = min(spp, batch)
+        np_pass = max(1, min(npix, batch // ns_chunk))
+        passes = -(-npix // np_pass) * -(-spp // ns_chunk)       # dragon: 960 px / 175 = 6
+        assert st["passes"] == passes
+        assert st["accumulate_launches"] == passes
