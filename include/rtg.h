@@ -652,6 +652,40 @@ int32_t rtg_render_aov(rtg_scene* scene, const rtg_camera_desc* cam, const rtg_r
 int32_t rtg_camera_rays(rtg_scene* scene, const rtg_camera_desc* cam, uint64_t seed, int32_t first_sample,
                         int32_t sample_count, rtg_ray* rays_out);
 
+/* ---- ABI 10 additions: an edge-avoiding denoiser for frames -------------------
+   Additive: the version stays 10, no struct grows.
+
+   rtg_denoise: an a-trous (dilated 5x5 B3-spline) wavelet filter over an image, stopped at edges of the
+   first-hit normal, of the depth (with a per-pixel slope) and, where a variance is given, of the
+   luminance (with a width in standard deviations of the 3x3-filtered variance).  With an albedo the
+   image is divided by max(albedo, 1/256) first and multiplied back afterwards, so texture detail is not
+   blurred.  A pixel is valid when its depth is finite and > 0 and its rgb and normal are finite; an
+   invalid pixel comes back as it went in, bit for bit, and feeds no other pixel.  A variance that is
+   negative or not finite counts as 0.  Float32 in a fixed order, no atomics: results repeat bit for
+   bit (the exact arithmetic: DESIGN.md §18).  Arguments are checked before the device is touched.
+   rgb_out may not alias an input. */
+typedef struct rtg_denoise_opts {   /* 32 bytes; NULL = all defaults */
+    int32_t iterations;         /* 0 = 5; 1..8; iteration i uses tap stride 2^i */
+    float   sigma_l;            /* 0 = 4.0f; luminance stop width in standard deviations */
+    float   sigma_z;            /* 0 = 1.0f; depth stop width in per-pixel slopes */
+    int32_t normal_power_log2;  /* 0 = 6 (power 64); 1..10: the normal stop is squared this many times */
+    int32_t pad[4];             /* must be 0 */
+} rtg_denoise_opts;
+typedef struct rtg_denoise_inputs { /* 40 bytes; ny*nx pixels each, [y][x][c] */
+    const float* rgb;       /* 3 per pixel: the image to filter (0..255 scale, unclamped) */
+    const float* normal;    /* 3 per pixel: rtg_render_aov's normal */
+    const float* depth;     /* 1 per pixel: rtg_render_aov's depth; <= 0 or non-finite: no surface */
+    const float* albedo;    /* 3 per pixel or NULL (no demodulation) */
+    const float* variance;  /* 1 per pixel or NULL (no luminance stop): variance of the pixel's MEAN
+                               luminance = rtg_frame_moments' variance / the pixel's sample count */
+} rtg_denoise_inputs;
+/* Host arrays; the work runs on HIP device `device`. */
+int32_t rtg_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t nx, int32_t ny,
+                    const rtg_denoise_opts* opts, float* rgb_out);
+/* Same on device arrays, enqueued on `stream` (hipStream_t); synchronous on return. */
+int32_t rtg_denoise_device(int32_t device, const rtg_denoise_inputs* in_device, int32_t nx, int32_t ny,
+                           const rtg_denoise_opts* opts, float* rgb_out_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

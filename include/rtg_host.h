@@ -77,6 +77,15 @@ extern int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, 
    _normal, _albedo and _depth before the extension: (normal * 0.5f + 0.5f) * 255.0f, albedo * 255.0f and
    the depth in all three channels.  (`extern` as above.) */
 extern int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir);
+/* rtgh_render_scene with a denoised image per camera (rtg_denoise): every camera goes through
+   one frame with moments whose samples are added in one go (the bits of rtg_render, so the image files are
+   byte-identical to rtgh_render_scene's); its image, filtered under the first-hit guides of its full sample
+   range with albedo demodulation and the variance of each pixel's mean luminance, is written through
+   rtgh_save_image, named like the camera's image with _denoised before the extension.  A one-sample camera
+   has no variance and is filtered without the luminance stop.  (`extern` as above.) */
+extern int32_t rtgh_render_scene_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir);
+/* The same, and rtgh_render_scene_aov's three feature images from the same guides. */
+extern int32_t rtgh_render_scene_denoise_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir);
 
 #ifdef __cplusplus
 }

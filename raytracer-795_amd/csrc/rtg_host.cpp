@@ -3741,6 +3741,71 @@ int32_t rtg_tonemap(int32_t device, const float* hdr, int32_t nx, int32_t ny, co
     });
 }
 
+// rtg_denoise's arguments, checked before the device is touched; *eff receives the options with defaults resolved.
+static int check_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t nx, int32_t ny, const rtg_denoise_opts* opts,
+                         const float* out, rtg_denoise_opts* eff) {
+    if (!in || !in->rgb || !in->normal || !in->depth || !out) return fail(RTG_ERR_INVALID, "null argument");
+    if (nx < 1 || ny < 1 || (long long)nx * ny > (1LL << 30)) return fail(RTG_ERR_INVALID, "denoise image size");
+    rtg_denoise_opts o{};
+    if (opts) o = *opts;
+    if (o.iterations < 0 || o.iterations > 8) return fail(RTG_ERR_INVALID, "denoise iterations must be 0 (default) or 1..8");
+    if (o.normal_power_log2 < 0 || o.normal_power_log2 > 10)
+        return fail(RTG_ERR_INVALID, "denoise normal_power_log2 must be 0 (default) or 1..10");
+    if (!std::isfinite(o.sigma_l) || !std::isfinite(o.sigma_z) || o.sigma_l < 0.0f || o.sigma_z < 0.0f)
+        return fail(RTG_ERR_INVALID, "denoise sigmas must be finite and not negative");
+    for (int i = 0; i < 4; i++)
+        if (o.pad[i] != 0) return fail(RTG_ERR_INVALID, "denoise options padding must be 0");
+    if (o.iterations == 0) o.iterations = 5;
+    if (o.sigma_l == 0.0f) o.sigma_l = 4.0f;
+    if (o.sigma_z == 0.0f) o.sigma_z = 1.0f;
+    if (o.normal_power_log2 == 0) o.normal_power_log2 = 6;
+    *eff = o;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return fail(RTG_ERR_NO_DEVICE, "no such device");
+    return RTG_OK;
+}
+
+int32_t rtg_denoise_device(int32_t device, const rtg_denoise_inputs* in, int32_t nx, int32_t ny, const rtg_denoise_opts* opts,
+                           float* out, void* stream) {
+    return guarded([&]() -> int32_t {
+        rtg_denoise_opts o{};
+        int rc = check_denoise(device, in, nx, ny, opts, out, &o);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(device));
+        std::string err;
+        if (denoise_device(*in, nx, ny, o, out, (hipStream_t)stream, err)) return fail(RTG_ERR_HIP, err);
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t nx, int32_t ny, const rtg_denoise_opts* opts,
+                    float* out) {
+    return guarded([&]() -> int32_t {
+        rtg_denoise_opts o{};
+        int rc = check_denoise(device, in, nx, ny, opts, out, &o);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(device));
+        const size_t np = (size_t)nx * ny;
+        // one allocation: rgb, normal, albedo, out (3 floats per pixel each), depth, variance (1 each)
+        struct Dev { float* p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } d;
+        if (hipMalloc(&d.p, sizeof(float) * 14 * np) != hipSuccess) return fail(RTG_ERR_OOM, "denoise buffers");
+        float *drgb = d.p, *dnormal = d.p + 3 * np, *dalbedo = d.p + 6 * np, *dout = d.p + 9 * np, *ddepth = d.p + 12 * np,
+              *dvar = d.p + 13 * np;
+        if (hipMemcpy(drgb, in->rgb, sizeof(float) * 3 * np, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dnormal, in->normal, sizeof(float) * 3 * np, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(ddepth, in->depth, sizeof(float) * np, hipMemcpyHostToDevice) != hipSuccess ||
+            (in->albedo && hipMemcpy(dalbedo, in->albedo, sizeof(float) * 3 * np, hipMemcpyHostToDevice) != hipSuccess) ||
+            (in->variance && hipMemcpy(dvar, in->variance, sizeof(float) * np, hipMemcpyHostToDevice) != hipSuccess))
+            return fail(RTG_ERR_HIP, "denoise upload");
+        rtg_denoise_inputs din{drgb, dnormal, ddepth, in->albedo ? dalbedo : nullptr, in->variance ? dvar : nullptr};
+        std::string err;
+        if (denoise_device(din, nx, ny, o, dout, nullptr, err)) return fail(RTG_ERR_HIP, err);
+        if (hipMemcpy(out, dout, sizeof(float) * 3 * np, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(RTG_ERR_HIP, "denoise download");
+        return RTG_OK;
+    });
+}
+
 int32_t rtg_scene_build_stats(const rtg_scene* s, rtg_build_stats* out) {
     if (!s || !out) return fail(RTG_ERR_INVALID, "null argument");
     *out = s->bst;

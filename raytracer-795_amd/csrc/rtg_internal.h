@@ -606,6 +606,11 @@ int tonemap_white_index(int n, float burn_percent);
 int tonemap_device(const float* hdr, int nx, int ny, const rtg_tonemap_desc& tm, float* out, hipStream_t st,
                    std::string& err);
 
+// Edge-avoiding a-trous denoiser (rtg_denoise.hip); every pointer of `in` and `out` are device
+// arrays, `o` holds the effective options (defaults resolved).
+int denoise_device(const rtg_denoise_inputs& in, int nx, int ny, const rtg_denoise_opts& o, float* out, hipStream_t st,
+                   std::string& err);
+
 // GPU BVH construction (rtg_bvh_gpu.hip): the reference median-split tree of one object.
 // nodes: breadth-first {left, right, start, end} (children -1: none); box: 6 floats per node
 // (min xyz, max xyz); perm: BVH position -> original primitive.  Inputs must be finite.

@@ -27,6 +27,13 @@
 // --aov also writes every camera's first-hit feature images over its full sample range (rtg_render_aov):
 // the shading normal as (n * 0.5 + 0.5) * 255, the albedo * 255 and the depth, named like the camera's image
 // with _normal, _albedo and _depth before the extension.  One GPU, not with --progressive.
+//
+//   rtg_cli scene.xml --denoise [--aov] [--device N] [--seed S] [--out-dir DIR]
+//
+// --denoise also writes every camera's image filtered by the edge-avoiding denoiser (rtg_denoise), guided by those
+// feature buffers and the per-pixel variance of a frame with moments, named with _denoised before the extension;
+// the image files themselves are the ones a run without it writes, byte for byte.  One GPU, in one go: not with
+// --progressive, --adaptive or --devices.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -39,7 +46,7 @@ int main(int argc, char** argv) {
     int device = 0, devices = 0, progressive = 0;
     bool have_progressive = false, have_target = false;
     double target_error = 0.0, adaptive = 0.0;
-    bool have_adaptive = false, have_min = false, aov = false;
+    bool have_adaptive = false, have_min = false, aov = false, denoise = false;
     int min_samples = 2;
     unsigned long long seed = 0x5EED2026ull;
     for (int i = 1; i < argc; i++) {
@@ -52,12 +59,13 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive = atof(argv[++i]); have_adaptive = true; }
         else if (!strcmp(argv[i], "--min-samples") && i + 1 < argc) { min_samples = atoi(argv[++i]); have_min = true; }
         else if (!strcmp(argv[i], "--aov")) aov = true;
+        else if (!strcmp(argv[i], "--denoise")) denoise = true;
         else if (argv[i][0] == '-') { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         else xml = argv[i];
     }
     if (!xml) {
         fprintf(stderr, "usage: %s scene.xml [--device N] [--devices G] [--seed S] [--out-dir DIR] "
-                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]]] [--aov]\n", argv[0]);
+                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]]] [--aov] [--denoise]\n", argv[0]);
         return 2;
     }
     if (have_progressive && devices > 0) {
@@ -66,6 +74,10 @@ int main(int argc, char** argv) {
     }
     if (aov && (have_progressive || devices > 0)) {
         fprintf(stderr, "rtg_cli: --aov renders on one GPU in one go: it cannot be combined with --devices or --progressive\n");
+        return 2;
+    }
+    if (denoise && (have_progressive || have_adaptive || devices > 0)) {
+        fprintf(stderr, "rtg_cli: --denoise renders on one GPU in one go: it cannot be combined with --devices, --progressive or --adaptive\n");
         return 2;
     }
     if ((have_progressive && progressive < 1) || (have_target && (!have_progressive || !(target_error >= 0.0)))) {
@@ -80,6 +92,8 @@ int main(int argc, char** argv) {
     }
     const int rc = have_adaptive ? rtgh_render_scene_adaptive(xml, device, seed, out_dir, progressive, adaptive, min_samples)
                  : have_progressive ? rtgh_render_scene_progressive(xml, device, seed, out_dir, progressive, target_error)
+                 : denoise          ? (aov ? rtgh_render_scene_denoise_aov(xml, device, seed, out_dir)
+                                           : rtgh_render_scene_denoise(xml, device, seed, out_dir))
                  : aov              ? rtgh_render_scene_aov(xml, device, seed, out_dir)
                                     : rtgh_render_scene_multi(xml, device, devices, seed, out_dir);
     if (rc != RTG_OK) {

@@ -1327,4 +1327,74 @@ int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint64_t see
     });
 }
 
+// rtgh_render_scene's camera loop with a denoised image per camera (rtg_denoise): one frame with
+// moments per camera, all its samples added at once (rtg_render's bits), the first-hit guides of the full sample
+// range, albedo demodulation, and the variance of each pixel's mean luminance where there are two samples.
+static int32_t render_scene_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir, bool aov) {
+    return guarded([&]() -> int32_t {
+        rtgh_scene* sc = nullptr;
+        int rc = rtgh_parse_xml(xml_path, &sc);
+        if (rc) return rc;
+        rtg_scene* gpu = nullptr;
+        rtg_build_opts bo{};
+        bo.bvh_builder = RTG_BVH_AUTO;
+        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
+        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
+        printf("BVH construction complete.\n");
+        for (const CamData& c : sc->cameras) {
+            const size_t np = (size_t)c.d.nx * c.d.ny;
+            std::vector<float> rgb(np * 3), normal(np * 3), albedo(np * 3), depth(np), var(np), img(np * 3);
+            rtg_render_opts o{};
+            o.seed = seed;
+            rtg_frame_opts fo{};
+            fo.moments = 1;
+            rtg_frame* fr = nullptr;
+            rc = rtg_frame_create(gpu, &c.d, &o, &fo, &fr);
+            if (rc) { g_err = rtg_last_error(); break; }
+            const int total = c.d.num_samples;
+            rtg_render_stats st{};
+            if ((rc = rtg_frame_add_samples(fr, total, nullptr)) == RTG_OK) {
+                rtg_last_render_stats(gpu, &st);
+                if ((rc = rtg_frame_resolve(fr, rgb.data())) == RTG_OK && total >= 2)
+                    rc = rtg_frame_moments(fr, nullptr, var.data());
+            }
+            if (rc) g_err = rtg_last_error();
+            rtg_frame_destroy(fr);
+            if (rc) break;
+            const std::string name = output_name(c, out_dir);
+            if ((rc = save_camera_images(c, name, rgb, device))) break;
+            rtg_aov_buffers ab{};
+            ab.depth = depth.data(); ab.normal = normal.data(); ab.albedo = albedo.data();
+            rc = rtg_render_aov(gpu, &c.d, &o, nullptr, &ab);
+            if (rc) { g_err = rtg_last_error(); break; }
+            if (aov) {
+                for (size_t i = 0; i < np * 3; i++) img[i] = (normal[i] * 0.5f + 0.5f) * 255.0f;
+                if ((rc = rtgh_save_image(aov_name(name, "_normal").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+                for (size_t i = 0; i < np * 3; i++) img[i] = albedo[i] * 255.0f;
+                if ((rc = rtgh_save_image(aov_name(name, "_albedo").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+                for (size_t i = 0; i < np * 3; i++) img[i] = depth[i / 3];
+                if ((rc = rtgh_save_image(aov_name(name, "_depth").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+            }
+            for (size_t i = 0; i < np; i++) var[i] = var[i] / (float)total;     // of the pixel's mean
+            rtg_denoise_inputs di{rgb.data(), normal.data(), depth.data(), albedo.data(), total >= 2 ? var.data() : nullptr};
+            rc = rtg_denoise(device, &di, c.d.nx, c.d.ny, nullptr, img.data());
+            if (rc) { g_err = rtg_last_error(); break; }
+            if ((rc = rtgh_save_image(aov_name(name, "_denoised").c_str(), img.data(), c.d.nx, c.d.ny))) break;
+            printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s; denoised\n", name.c_str(), st.render_ms,
+                   st.total_rays / (st.render_ms * 1e3), st.devices, st.devices == 1 ? "" : "s");
+        }
+        rtg_scene_destroy(gpu);
+        rtgh_free(sc);
+        return rc;
+    });
+}
+
+int32_t rtgh_render_scene_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
+    return render_scene_denoise(xml_path, device, seed, out_dir, false);
+}
+
+int32_t rtgh_render_scene_denoise_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
+    return render_scene_denoise(xml_path, device, seed, out_dir, true);
+}
+
 }  // extern "C"

@@ -6,8 +6,8 @@ mirror of the reference's Parser / Scene::renderScene() / Image interface.
 """
 from . import _abi
 from ._abi import RtgError, load_library
-from .render import Comm, Frame, Renderer, render_scene, save_image, tonemap
+from .render import Comm, Frame, Renderer, denoise, render_scene, save_image, tonemap
 from .scene import Camera, Instance, Light, Material, Object, Scene, Texture, parse_xml, write_xml
 
-__all__ = ["RtgError", "load_library", "Comm", "Frame", "Renderer", "render_scene", "save_image", "tonemap", "Camera", "Instance", "Light",
+__all__ = ["RtgError", "load_library", "Comm", "Frame", "Renderer", "render_scene", "save_image", "tonemap", "denoise", "Camera", "Instance", "Light",
            "Material", "Object", "Scene", "Texture", "parse_xml", "write_xml", "_abi"]

@@ -194,6 +194,15 @@ class AovBuffers(C.Structure):
     _fields_ = [("hits", PI), ("depth", PF), ("normal", PF), ("albedo", PF), ("ids", PI)]
 
 
+class DenoiseOpts(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("normal_power_log2", C.c_int32), ("pad", C.c_int32 * 4)]
+
+
+class DenoiseInputs(C.Structure):
+    _fields_ = [("rgb", PF), ("normal", PF), ("depth", PF), ("albedo", PF), ("variance", PF)]
+
+
 class Hit(C.Structure):
     _fields_ = [("full", C.c_int32), ("object", C.c_int32), ("prim", C.c_int32), ("material", C.c_int32),
                 ("t", C.c_float), ("point", F3), ("normal", F3)]
@@ -253,6 +262,10 @@ EXPORTS = {
                                    C.POINTER(AovBuffers)]),
     "rtg_camera_rays": (C.c_int32, [C.c_void_p, C.POINTER(CameraDesc), C.c_uint64, C.c_int32, C.c_int32,
                                     C.POINTER(Ray)]),
+    # ABI 10 additions: the edge-avoiding denoiser
+    "rtg_denoise": (C.c_int32, [C.c_int32, C.POINTER(DenoiseInputs), C.c_int32, C.c_int32, C.POINTER(DenoiseOpts), PF]),
+    "rtg_denoise_device": (C.c_int32, [C.c_int32, C.POINTER(DenoiseInputs), C.c_int32, C.c_int32,
+                                       C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -49,6 +49,10 @@ def load():
         lib.rtgh_render_scene_adaptive.restype = C.c_int32
         lib.rtgh_render_scene_aov.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p]
         lib.rtgh_render_scene_aov.restype = C.c_int32
+        lib.rtgh_render_scene_denoise.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p]
+        lib.rtgh_render_scene_denoise.restype = C.c_int32
+        lib.rtgh_render_scene_denoise_aov.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p]
+        lib.rtgh_render_scene_denoise_aov.restype = C.c_int32
         lib.rtgh_read_image.argtypes = [C.c_char_p, C.POINTER(A.PF), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.rtgh_read_image.restype = C.c_int32
         lib.rtgh_free_image.argtypes = [A.PF]
@@ -148,6 +152,14 @@ def render_scene_aov(xml_path: str, device: int = 0, seed: int = 0x5EED2026, out
     """rtgh_render_scene_aov: every camera's image and its _normal / _albedo / _depth feature images."""
     lib = load()
     _check(lib.rtgh_render_scene_aov(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None))
+
+
+def render_scene_denoise(xml_path: str, device: int = 0, seed: int = 0x5EED2026, out_dir: str | None = None,
+                         aov: bool = False):
+    """rtgh_render_scene_denoise: every camera's image and its _denoised image (with `aov` the feature images too)."""
+    lib = load()
+    fn = lib.rtgh_render_scene_denoise_aov if aov else lib.rtgh_render_scene_denoise
+    _check(fn(xml_path.encode(), device, seed, out_dir.encode() if out_dir else None))
 
 
 def _struct(s) -> dict:

@@ -290,7 +290,7 @@ class Comm:
             pass
 
 
-def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed: int = DEFAULT_SEED, aov: bool = False) -> list:
+def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed: int = DEFAULT_SEED, aov: bool = False, denoise: bool = False) -> list:
     """Scene::renderScene (src/Scene.cpp:294-363): every camera rendered and saved.  A camera
     with a hw5 <Tonemap> also gets its tone-mapped image (tonemapped_name; a .png ImageName is
     written tone-mapped instead of clamped)."""
@@ -298,7 +298,8 @@ def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed
     print("BVH construction complete.")
     with Renderer(scene, device) as r:
         for cam in scene.cameras:
-            img = r.render(cam, seed=seed)
+            den = _render_denoised(r, cam, seed) if denoise else None     # rtg_cli --denoise
+            img = r.render(cam, seed=seed) if den is None else den[0]
             name = cam.image_name if out_dir is None else os.path.join(out_dir, os.path.basename(cam.image_name))
             tm = None if cam.tonemap is None else tonemap(img, *cam.tonemap, device=device)
             if tm is None or not _is_png(name):
@@ -308,7 +309,17 @@ def render_scene(scene: Scene, out_dir: str | None = None, device: int = 0, seed
             if aov:      # rtg_cli --aov: the feature images over the camera's full sample range
                 for suffix, data in aov_images(r.aov(cam, seed=seed)):
                     written.append(save_image(aov_name(name, suffix), data))
+            if den is not None:
+                written.append(save_image(denoised_name(name), den[1]))
     return written
+
+
+def _render_denoised(r: Renderer, cam: Camera, seed: int):
+    """(image, denoised image) of a camera through one frame with moments: all samples added at once
+    resolve to Renderer.render's bits."""
+    with r.frame(cam, moments=True, seed=seed) as f:
+        f.add(cam.num_samples)
+        return f.resolve(), f.denoise()
 
 
 def aov_name(name: str, suffix: str) -> str:
@@ -513,3 +524,67 @@ def _renderer_camera_rays(self, camera: Camera | int = 0, first_sample: int = 0,
 # (methods of Renderer, defined here so that the lines above them stay where they are)
 Renderer.aov = _renderer_aov
 Renderer.camera_rays = _renderer_camera_rays
+
+
+# ---------------------------------------------------------------------------- denoiser
+def denoise(img: np.ndarray, normal: np.ndarray, depth: np.ndarray, albedo=None, variance=None, iterations: int = 0,
+            sigma_l: float = 0.0, sigma_z: float = 0.0, normal_power_log2: int = 0, device: int = 0) -> np.ndarray:
+    """Edge-avoiding à-trous filter on the GPU (rtg_denoise): `img` (ny, nx, 3) guided by Renderer.aov's
+    `normal` (ny, nx, 3) and `depth` (ny, nx); `albedo` (ny, nx, 3) demodulates, `variance` (ny, nx), the
+    variance of each pixel's mean luminance, opens the luminance stop.  An option of 0 takes its default
+    (5 iterations, sigma_l 4, sigma_z 1, normal power 2^6)."""
+    lib = A.load_library()
+    a = np.ascontiguousarray(img, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("image must be (ny, nx, 3)")
+    ny, nx = a.shape[:2]
+
+    def guide(v, shape, what):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, np.float32)
+        if v.shape != shape:
+            raise ValueError(f"{what} must be {shape}")
+        return v
+
+    n = guide(normal, (ny, nx, 3), "normal")
+    z = guide(depth, (ny, nx), "depth")
+    al = guide(albedo, (ny, nx, 3), "albedo")
+    var = guide(variance, (ny, nx), "variance")
+    if n is None or z is None:
+        raise ValueError("normal and depth are required")
+    out = np.zeros_like(a)
+    ptr = lambda v: None if v is None else v.ctypes.data_as(A.PF)
+    di = A.DenoiseInputs(ptr(a), ptr(n), ptr(z), ptr(al), ptr(var))
+    do = A.DenoiseOpts(int(iterations), float(sigma_l), float(sigma_z), int(normal_power_log2))
+    A.check(lib.rtg_denoise(int(device), C.byref(di), nx, ny, C.byref(do), out.ctypes.data_as(A.PF)), lib)
+    return out
+
+
+def denoised_name(name: str) -> str:
+    """Where a camera's denoised image goes: _denoised before its ImageName's extension."""
+    return aov_name(name, "_denoised")
+
+
+def _frame_denoise(self, demodulate: bool = True, **opts) -> np.ndarray:
+    """The frame's resolve() filtered by rtg.denoise under the camera's first-hit guides (Renderer.aov over
+    its whole sample range, the frame's seed and traversal).  With moments and at least two samples the
+    luminance stop runs on moments()[1] / counts()[0], the variance of each pixel's mean (0 for a pixel with
+    fewer than two samples).  `opts`: denoise's options.  Whole, uncompacted frames only."""
+    o = self.opts
+    if o.compact_rows or o.row_stride > 1 or self.rows != self.camera.ny or o.num_devices > 0 or bool(o.devices):
+        raise ValueError("Frame.denoise needs a whole frame: not sharded, not compact")
+    if self.samples_done < 1:
+        raise ValueError("Frame.denoise on a frame without samples")
+    img = self.resolve()
+    g = self.renderer.aov(self.camera, seed=o.seed, traversal=o.traversal)
+    var = None
+    if self.has_moments and self.samples_done >= 2:
+        cnt = self.counts()[0]
+        var = (self.moments()[1] / np.maximum(cnt, 1).astype(np.float32)).astype(np.float32)
+        var[cnt < 2] = 0
+    return denoise(img, g["normal"], g["depth"], g["albedo"] if demodulate else None, var, device=self.renderer.device,
+                   **opts)
+
+
+Frame.denoise = _frame_denoise

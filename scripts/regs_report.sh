@@ -1,24 +1,27 @@
 #!/bin/bash
-# VGPR / SGPR / spill / scratch of the traversal and shading kernels in a gfx950 build of rtg_device.hip
+# VGPR / SGPR / spill / scratch of the traversal and shading kernels in a gfx950 build of rtg_device.hip and of
+# the denoiser's kernels in rtg_denoise.hip (with their static LDS)
 # (dev tool: cross-compiles the device code to assembly and reads its kernel metadata).
 #   bash scripts/regs_report.sh [extra hipcc flags]
 set -e
 cd "$(dirname "$0")/../raytracer-795_amd/csrc"
+for unit in rtg_device rtg_denoise; do
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
   -fno-gpu-flush-denormals-to-zero -Xclang -target-feature -Xclang -packed-fp32-ops --offload-device-only -S \
-  -o /tmp/rtg_dev.s rtg_device.hip "$@" 2>&1 | grep -v "not a recognized\|hip-link" || true
+  -o /tmp/$unit.s $unit.hip "$@" 2>&1 | grep -v "not a recognized\|hip-link" || true
+done
 python3 - <<'PY'
 import re
-s = open('/tmp/rtg_dev.s').read()
-for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.vgpr_count:\s+(\d+)', s, re.S):
-    pass
-# amdhsa metadata blocks: one per kernel
-for blk in s.split('  - .agpr_count')[1:]:
-    name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-    if not re.search(r'k_(trace|shadow|shade|pt_shade|aov)', name):
-        continue
-    g = lambda k: (re.search(r'\.' + k + r':\s+(\d+)', blk) or [0, '?'])[1]
-    dem = name.replace('_ZN3rtg', '')[:60]
-    print(f"{dem:60s} vgpr {g('vgpr_count'):>4} sgpr {g('sgpr_count'):>4} vspill {g('vgpr_spill_count'):>4} "
-          f"sspill {g('sgpr_spill_count'):>4} scratch {g('private_segment_fixed_size'):>5}")
+for unit in ('rtg_device', 'rtg_denoise'):
+    s = open(f'/tmp/{unit}.s').read()
+    # amdhsa metadata blocks: one per kernel
+    for blk in s.split('  - .agpr_count')[1:]:
+        name = re.search(r'\.name:\s+(\S+)', blk).group(1)
+        if not re.search(r'k_(trace|shadow|shade|pt_shade|aov|dn)', name):
+            continue
+        g = lambda k: (re.search(r'\.' + k + r':\s+(\d+)', blk) or [0, '?'])[1]
+        dem = re.sub(r'_ZN3rtg(\d+_GLOBAL__N_1)?', '', name)[:60]
+        lds = f" lds {g('group_segment_fixed_size'):>6}" if unit == 'rtg_denoise' else ""
+        print(f"{dem:60s} vgpr {g('vgpr_count'):>4} sgpr {g('sgpr_count'):>4} vspill {g('vgpr_spill_count'):>4} "
+              f"sspill {g('sgpr_spill_count'):>4} scratch {g('private_segment_fixed_size'):>5}{lds}")
 PY
