@@ -1423,35 +1423,146 @@ static TriGeom tri_geom(const std::vector<V3>& verts, const std::vector<int>& pv
     return tg;
 }
 
-static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
-    PhaseClock pc;
-    rtg_build_stats& bs = s->bst;
+}  // extern "C"
+
+namespace {
+
+// A thread that is joined when it leaves scope: declare it after everything it reads.
+struct ScopedThread {
+    std::thread t;
+    ~ScopedThread() { if (t.joinable()) t.join(); }
+};
+
+inline bool is_leaf(const HNode& n) { return n.left < 0 && n.right < 0; }
+
+// One partial result per chunk of [0, n), body(begin, end), folded in chunk order starting from
+// `init` (the value a chunk that did not run keeps, so fold must absorb it).
+template <class T, class Body, class Fold>
+T chunk_reduce(size_t n, size_t grain, T init, Body&& body, Fold&& fold) {
+    static_assert(!std::is_same<T, bool>::value, "vector<bool> packs bits: chunks would race");
+    std::vector<T> part(build_threads(), init);
+    parallel_chunks(n, grain, [&](int ch, size_t k0, size_t k1) { part[ch] = body(k0, k1); });
+    T r = init;
+    for (const T& v : part) r = fold(r, v);
+    return r;
+}
+
+// p2.yzw of a triangle record is the caller's (tri_geom): the record's reference position, the
+// first position of its reference leaf, and whether that leaf's parent box gates it.
+inline void set_tri_ref(TriGeom& t, int pos, int leaf_start, int gated) {
+    memcpy(&t.p2.y, &pos, 4);
+    memcpy(&t.p2.z, &leaf_start, 4);
+    memcpy(&t.p2.w, &gated, 4);
+}
+
+// rows 0-2 of `inv` the identity up to the signs of its zeros (compared by value), zero blur
+bool unit_transform(const float inv[16], const float blur[3]) {
+    bool unit = true;
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++) unit = unit && inv[c * 4 + r] == (c == r ? 1.0f : 0.0f);
+    for (int k = 0; k < 3; k++) unit = unit && blur[k] == 0.0f;
+    return unit;
+}
+
+// Every host array the scene build produces (the rest of its output lives in the rtg_scene).  One
+// instance per build_scene call; the phases below take it by reference.
+//
+// dnodes, gates, tris and primidx, with s->orig_prim and s->vnormals, are frozen from
+// start_early_upload() on: the `early` thread reads them until it is joined, so the phases that run
+// after it take them as const (or not at all).  `early` is the last member: it is joined before any
+// array is destroyed, on every return path and on an exception.
+struct SceneArrays {
+    std::vector<V3> verts, vn;
+    std::vector<std::vector<int>> prims;     // per object, parse order: 3 per prim (sphere: center,0,0)
+    std::vector<Mat4> model;                 // per object
+    std::vector<Mat4> top_model;             // per top-level entry (objects, then instances)
+
+    std::vector<Geometry> geoms;
+    hvec<Node> dnodes;
+    hvec<Node4> snodes;                      // traversal trees (SAH, 4-wide)
+    hvec<TriGeom> stris;                     // their triangles, SAH leaf order (p2 = ref position / leaf / gated)
+    hvec<float> gates;                       // per reference position: its leaf's parent box
+    hvec<TriGeom> tris;
+    hvec<int4> primidx;
+    std::vector<int> pos_leaf;               // per reference position: first position of its leaf ...
+    std::vector<char> pos_gated;             // ... and whether its leaf's parent (gates[]) is not the root
+    std::vector<char> geom_finite;           // per object: every primitive box coordinate finite
+
+    std::vector<TopObject> tops;
+    std::vector<SphereEnt> tsph;
+    std::vector<Node> tlas_nodes;
+    std::vector<int> tlas_idx;
+    std::vector<TriGeom> gtris;
+    std::vector<GroupEnt> gents;
+    std::vector<TopObject> gtop;
+
+    std::vector<MaterialDev> mats;
+    std::vector<TextureDev> texs;
+    std::vector<float> texels;
+    std::vector<LightDev> lights;
+    std::vector<int> top_emit;
+    std::vector<float> etris, ecdf;
+    std::vector<float> vflat, tcflat;
+
+    bool early_upload = false;               // the frozen arrays were uploaded by `early`
+    int early_rc = RTG_OK;
+    std::string early_err;                   // its rtg_last_error() (thread-local there)
+    ScopedThread early;
+};
+
+// The reference-tree records: uploaded by the early thread, or with the rest when there was none.
+int upload_reference_records(rtg_scene* s, const SceneArrays& A) {
+    int rc;
+    if ((rc = upload(s->d_nodes, A.dnodes)) || (rc = upload(s->d_gates, A.gates)) || (rc = upload(s->d_tris, A.tris)) ||
+        (rc = upload(s->d_primidx, A.primidx)) || (rc = upload(s->d_origprim, s->orig_prim)) ||
+        (rc = upload(s->d_vnormals, s->vnormals)))
+        return rc;
+    return RTG_OK;
+}
+
+// The last object's reference-tree records are final now: a helper thread uploads them while
+// this one finishes the traversal tree and the top level (joined before the remaining uploads;
+// nothing below writes these arrays).  Dragon1m: ~7-10 ms of host-to-device copies.
+void start_early_upload(rtg_scene* s, SceneArrays& A) {
+    const SceneArrays& frozen = A;
+    A.early.t = std::thread([s, &frozen, &rc = A.early_rc, &err = A.early_err, dev = s->device] {
+        if (hipSetDevice(dev) != hipSuccess) { rc = RTG_ERR_HIP; err = "hipSetDevice"; return; }
+        if (int rc2 = upload_reference_records(s, frozen)) {
+            rc = rc2;
+            err = rtg_last_error();
+        }
+    });
+    A.early_upload = true;
+}
+
+// Geometry preparation: vertices, per-object primitive lists, matrices, smooth vertex normals.
+void prepare_geometry(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
     const int nv = d->num_vertices;
-    std::vector<V3> verts(nv);
+    std::vector<V3>& verts = A.verts;
+    verts.resize(nv);
     for (int i = 0; i < nv; i++) verts[i] = v3(d->vertices[3 * i], d->vertices[3 * i + 1], d->vertices[3 * i + 2]);
     s->num_objects = d->num_objects;
     s->num_instances = d->num_instances;
     s->num_vertices = nv;
 
     // per-object primitive lists in parse order
-    struct ObjPrims { std::vector<int> v; };   // 3 per prim (sphere: center,0,0)
-    std::vector<ObjPrims> op(d->num_objects);
+    A.prims.resize(d->num_objects);
     for (int i = 0; i < d->num_objects; i++) {
         const rtg_object_desc& o = d->objects[i];
-        if (o.type == RTG_OBJ_MESH) op[i].v.assign(d->faces + 3 * o.face_first, d->faces + 3 * (o.face_first + o.face_count));
-        else if (o.type == RTG_OBJ_TRIANGLE) op[i].v = {o.v[0], o.v[1], o.v[2]};
-        else op[i].v = {o.center, 0, 0};
+        if (o.type == RTG_OBJ_MESH) A.prims[i].assign(d->faces + 3 * o.face_first, d->faces + 3 * (o.face_first + o.face_count));
+        else if (o.type == RTG_OBJ_TRIANGLE) A.prims[i] = {o.v[0], o.v[1], o.v[2]};
+        else A.prims[i] = {o.center, 0, 0};
     }
 
     // matrices (objects, then instances)
-    std::vector<Mat4> model(d->num_objects);
-    std::vector<Mat4> top_model;             // per top-level entry (objects, then instances)
+    std::vector<Mat4>& model = A.model;
+    model.resize(d->num_objects);
     s->inv.clear(); s->invT.clear();
     for (int i = 0; i < d->num_objects; i++) {
         model[i] = compose(d, d->objects[i].xform_first, d->objects[i].xform_count);
         s->inv.push_back(inverse(model[i]));
         s->invT.push_back(inverse_transpose(model[i]));
-        top_model.push_back(model[i]);
+        A.top_model.push_back(model[i]);
     }
     for (int i = 0; i < d->num_instances; i++) {
         const rtg_instance_desc& in = d->instances[i];
@@ -1459,15 +1570,16 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         if (!in.reset_transform) m = mul(m, model[in.base_object]);
         s->inv.push_back(inverse(m));
         s->invT.push_back(inverse_transpose(m));
-        top_model.push_back(m);
+        A.top_model.push_back(m);
     }
 
     // smooth vertex normals (src/Scene.cpp:302-318)
-    std::vector<V3> vn(nv, v3(0, 0, 0));
+    std::vector<V3>& vn = A.vn;
+    vn.assign(nv, v3(0, 0, 0));
     for (int i = 0; i < d->num_objects; i++) {
         const rtg_object_desc& o = d->objects[i];
         if (!(o.type == RTG_OBJ_TRIANGLE || (o.type == RTG_OBJ_MESH && o.smooth))) continue;
-        const std::vector<int>& pv = op[i].v;
+        const std::vector<int>& pv = A.prims[i];
         for (size_t k = 0; k + 2 < pv.size(); k += 3) {
             V3 a = verts[pv[k] - 1], b = verts[pv[k + 1] - 1], c = verts[pv[k + 2] - 1];
             V3 n = normalized(cross(c - b, a - b));
@@ -1479,438 +1591,507 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         V3 n = normalized(vn[i]);
         s->vnormals[3 * i] = n.x; s->vnormals[3 * i + 1] = n.y; s->vnormals[3 * i + 2] = n.z;
     }
-    bs.prep_ms += pc.lap("prep");
+}
 
-    // BVHs and device geometry
-    std::vector<Geometry> geoms(d->num_objects);
-    hvec<Node> dnodes;
-    hvec<Node4> snodes;                      // traversal trees (SAH, 4-wide)
-    hvec<TriGeom> stris;                     // their triangles, SAH leaf order (p2 = ref position / leaf / gated)
-    hvec<float> gates;                       // per reference position: its leaf's parent box
-    hvec<TriGeom> tris;
-    std::vector<int> pos_leaf;               // per reference position: first position of its leaf ...
-    std::vector<char> pos_gated;             // ... and whether its leaf's parent (gates[]) is not the root
-    std::vector<char> geom_finite(d->num_objects, 0);   // every primitive box coordinate finite
-    hvec<int4> primidx;
-    bool early_upload = false;               // dnodes / gates / tris / primidx / orig_prim / vnormals uploaded by early_thread
-    std::thread early_thread;
-    int early_rc = RTG_OK;
-    std::string early_err;                   // early_thread's rtg_last_error() (thread-local there)
-    struct EarlyJoin {                       // joined on every return path (the thread reads this frame's arrays)
-        std::thread& t;
-        ~EarlyJoin() { if (t.joinable()) t.join(); }
-    } early_join{early_thread};
-    s->orig_prim.clear();
-    s->bvh.assign(d->num_objects, ObjBVH());
-    const float ieps = d->intersection_test_eps;
-    for (int i = 0; i < d->num_objects; i++) {
-        const rtg_object_desc& o = d->objects[i];
-        const std::vector<int>& pv = op[i].v;
-        int np = (int)(pv.size() / 3);
-        hvec<V3> centers(np), bmin(np), bmax(np);
-        std::vector<char> fin_chunk(std::max(build_threads(), 1), 1);
-        parallel_chunks((size_t)np, 1 << 14, [&](int ch, size_t k0, size_t k1) {
-            bool fin = true;
+// One object's build state, alive for its iteration of the object loop (build_object).
+struct ObjWork {
+    const rtg_object_desc& o;
+    const std::vector<int>& pv;              // its primitive list (SceneArrays::prims)
+    const int np;
+    hvec<V3> centers, bmin, bmax;            // per primitive, parse order
+    bool all_finite = false;                 // every centre and box coordinate finite
+    float obj_pad = 0.0f;                    // the eps overhang (primitive_boxes)
+    hvec<int> dev_index;                     // per reference-tree node: its dnodes index, -1 for a leaf
+    std::vector<int> leaf_start;             // per position of the object: its leaf's first position (scene-wide)
+    std::vector<char> gated;                 // ... and whether the leaf's parent is not the root
+};
+
+// Primitive boxes and centres, whether all are finite, and the eps pad.
+void primitive_boxes(const std::vector<V3>& verts, float ieps, ObjWork& w) {
+    const rtg_object_desc& o = w.o;
+    const std::vector<int>& pv = w.pv;
+    const int np = w.np;
+    hvec<V3>&centers = w.centers, &bmin = w.bmin, &bmax = w.bmax;
+    centers.resize(np); bmin.resize(np); bmax.resize(np);
+    w.all_finite = chunk_reduce<char>((size_t)np, 1 << 14, 1, [&](size_t k0, size_t k1) -> char {
+        bool fin = true;
+        for (size_t k = k0; k < k1; k++) {
+            if (o.type == RTG_OBJ_SPHERE) {                            // Shape.cpp:55-67
+                V3 c = verts[o.center - 1];
+                float R = o.radius;
+                centers[k] = c;
+                bmin[k] = v3(c.x - R, c.y - R, c.z - R);
+                bmax[k] = v3(c.x + R, c.y + R, c.z + R);
+            } else {                                                  // Shape.cpp:162-190
+                V3 a = verts[pv[3 * k] - 1], b = verts[pv[3 * k + 1] - 1], c = verts[pv[3 * k + 2] - 1];
+                centers[k] = v3(((a.x + b.x) + c.x) / 3.0f, ((a.y + b.y) + c.y) / 3.0f, ((a.z + b.z) + c.z) / 3.0f);
+                bmin[k] = v3(minOf3(a.x, b.x, c.x), minOf3(a.y, b.y, c.y), minOf3(a.z, b.z, c.z));
+                bmax[k] = v3(maxOf3(a.x, b.x, c.x), maxOf3(a.y, b.y, c.y), maxOf3(a.z, b.z, c.z));
+            }
+            fin = fin && std::isfinite(centers[k].x) && std::isfinite(centers[k].y) && std::isfinite(centers[k].z) &&
+                  std::isfinite(bmin[k].x) && std::isfinite(bmin[k].y) && std::isfinite(bmin[k].z) &&
+                  std::isfinite(bmax[k].x) && std::isfinite(bmax[k].y) && std::isfinite(bmax[k].z);
+        }
+        return fin;
+    }, [](char a, char b) -> char { return a && b; });
+    // the eps overhang of a candidate beyond its triangle (Triangle::bvhIntersect's t >= -eps):
+    // the traversal tree's boxes and the root window are widened by it (a max over the faces,
+    // so the evaluation order does not matter)
+    if (o.type != RTG_OBJ_SPHERE)
+        w.obj_pad = chunk_reduce<float>((size_t)np, 1 << 14, 0.0f, [&](size_t k0, size_t k1) {
+            float padc = 0.0f;
             for (size_t k = k0; k < k1; k++) {
-                if (o.type == RTG_OBJ_SPHERE) {                            // Shape.cpp:55-67
-                    V3 c = verts[o.center - 1];
-                    float R = o.radius;
-                    centers[k] = c;
-                    bmin[k] = v3(c.x - R, c.y - R, c.z - R);
-                    bmax[k] = v3(c.x + R, c.y + R, c.z + R);
-                } else {                                                  // Shape.cpp:162-190
-                    V3 a = verts[pv[3 * k] - 1], b = verts[pv[3 * k + 1] - 1], c = verts[pv[3 * k + 2] - 1];
-                    centers[k] = v3(((a.x + b.x) + c.x) / 3.0f, ((a.y + b.y) + c.y) / 3.0f, ((a.z + b.z) + c.z) / 3.0f);
-                    bmin[k] = v3(minOf3(a.x, b.x, c.x), minOf3(a.y, b.y, c.y), minOf3(a.z, b.z, c.z));
-                    bmax[k] = v3(maxOf3(a.x, b.x, c.x), maxOf3(a.y, b.y, c.y), maxOf3(a.z, b.z, c.z));
-                }
-                fin = fin && std::isfinite(centers[k].x) && std::isfinite(centers[k].y) && std::isfinite(centers[k].z) &&
-                      std::isfinite(bmin[k].x) && std::isfinite(bmin[k].y) && std::isfinite(bmin[k].z) &&
-                      std::isfinite(bmax[k].x) && std::isfinite(bmax[k].y) && std::isfinite(bmax[k].z);
+                const V3 a = verts[pv[3 * k] - 1], b = verts[pv[3 * k + 1] - 1], c = verts[pv[3 * k + 2] - 1];
+                const double e = (double)(ieps > 0 ? ieps : 0.0f);
+                const double ext = e * ((double)vnorm(b - a) + (double)vnorm(c - a));
+                padc = std::max(padc, (float)(ext * 1.02 + 1e-7));
             }
-            fin_chunk[ch] = fin;
-        });
-        bool all_finite = true;
-        for (char f : fin_chunk) all_finite = all_finite && f;
-        geom_finite[i] = all_finite;
-        // traversal tree (SAH, 4-wide; below) of a triangle object with finite primitives: its
-        // binned-SAH recursion runs on its own threads, over the triangles in parse order, while the
-        // reference's median tree is built (on the GPU for large meshes); its leaves are mapped to
-        // reference positions afterwards.  Any tree shape gives the same results (the total order
-        // of candidates and the reachability gates), so it needs no reference order.
-        const bool sah_try = o.type != RTG_OBJ_SPHERE && np >= 2 && all_finite && s->blas_mode != 1;
-        // the eps overhang of a candidate beyond its triangle (Triangle::bvhIntersect's t >= -eps):
-        // the traversal tree's boxes and the root window are widened by it (a max over the faces,
-        // so the evaluation order does not matter)
-        float obj_pad = 0.0f;
-        if (o.type != RTG_OBJ_SPHERE) {
-            std::vector<float> pad_chunk(build_threads(), 0.0f);
-            parallel_chunks((size_t)np, 1 << 14, [&](int ch, size_t k0, size_t k1) {
-                float padc = 0.0f;
-                for (size_t k = k0; k < k1; k++) {
-                    const V3 a = verts[pv[3 * k] - 1], b = verts[pv[3 * k + 1] - 1], c = verts[pv[3 * k + 2] - 1];
-                    const double e = (double)(ieps > 0 ? ieps : 0.0f);
-                    const double ext = e * ((double)vnorm(b - a) + (double)vnorm(c - a));
-                    padc = std::max(padc, (float)(ext * 1.02 + 1e-7));
-                }
-                pad_chunk[ch] = padc;
-            });
-            for (float x : pad_chunk) obj_pad = std::max(obj_pad, x);
-        }
-        hvec<SahRec> sah_rec_buf, sah_tmp;
-        hvec<int> sah_idx;
-        std::vector<SahNode2> sah_bn;            // host build (the GPU build collapses on the device)
-        bool sah_root_interior = false;
-        uint64_t sah_hash = 0, sah_bnodes = 0;
-        // the traversal tree on the GPU: large meshes of a device scene (the host recursion was the
-        // long pole of scene creation, ~75-85 ms for the dragon on its thread)
-        const bool sah_gpu = s->device >= 0 && (s->bvh_builder == RTG_BVH_GPU ||
-                                                (s->bvh_builder == RTG_BVH_AUTO && np >= kSahGpuMin));
-        // the SAH thread also collapses its tree to 4-wide nodes (leaf refs from tri_base0, the
-        // object's first traversal-order triangle) and forms the triangles' records in that order
-        // (p2.yzw, which need the reference tree, are filled after the join)
-        const int tri_base0 = (int)stris.size();
-        hvec<Node4> sah_nodes;
-        hvec<TriGeom> sah_tris;
-        std::thread sah_thread;
-        std::exception_ptr sah_err;
-        struct Joiner {                    // the SAH thread never outlives this iteration
-            std::thread& t;
-            ~Joiner() { if (t.joinable()) t.join(); }
-        } sah_join{sah_thread};
-        if (sah_try) {
-            sah_rec_buf.resize(np);
-            if (!sah_gpu) sah_tmp.resize(np);
-            sah_idx.resize(np);
-            parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
-                for (size_t f = k0; f < k1; f++) {
-                    SahRec& q = sah_rec_buf[f];
-                    for (int z = 0; z < 3; z++) { q.lo[z] = comp(bmin[f], z); q.hi[z] = comp(bmax[f], z); }
-                    q.idx = (int)f;
-                    q.pad_ = 0;
-                }
-            });
-            if (!sah_gpu) sah_bn.reserve(2 * (size_t)np / kSahMaxLeaf + 16);
-            sah_thread = std::thread([&] {
-                try {
-                    PhaseClock tc;
-                    if (sah_gpu) {                   // tree, collapse and hash on the device
-                        std::string e;
-                        if (hipSetDevice(s->device) != hipSuccess)
-                            throw std::runtime_error("GPU SAH build: hipSetDevice failed");
-                        auto alloc4 = [&](size_t c) { sah_nodes.resize(c); return sah_nodes.data(); };
-                        if (gpu_build_sah(sah_rec_buf.data(), np, tri_base0, obj_pad, alloc4, sah_idx.data(), sah_bnodes,
-                                          sah_hash, e))
-                            throw std::runtime_error("GPU SAH build: " + e);
-                        sah_root_interior = !sah_nodes.empty();
-                        tc.lap(" sah_tree+collapse gpu (thread)");
-                        if (sah_root_interior) {
-                            node4_preorder(sah_nodes);
-                            tc.lap(" node4 preorder (thread)");
-                        }
-                    } else {
-                        sah_rec_par(sah_rec_buf.data(), sah_tmp.data(), 0, np, sah_bn, sah_depth());
-                        parallel_chunks((size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
-                            for (size_t k = k0; k < k1; k++) sah_idx[k] = sah_rec_buf[k].idx;
-                        });
-                        tc.lap(" sah_tree (thread)");
-                        sah_tree_stats(sah_bn.data(), 0, sah_bnodes, sah_hash);
-                        sah_root_interior = sah_bn[0].left >= 0;
-                        if (sah_root_interior) {
-                            sah_nodes.reserve((size_t)np / 2 + 16);
-                            sah_collapse_par(sah_bn.data(), 0, tri_base0, obj_pad, sah_nodes, 3);
-                            tc.lap(" sah_collapse (thread)");
-                        }
-                    }
-                    if (sah_root_interior) {
-                        sah_tris.resize(np);
-                        parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
-                            for (size_t k = k0; k < k1; k++) sah_tris[k] = tri_geom(verts, pv, (size_t)sah_idx[k]);
-                        });
-                        tc.lap(" sah_tris (thread)");
-                    }
-                } catch (...) {
-                    sah_err = std::current_exception();
-                }
-            });
-        }
-        ObjBVH& ob = s->bvh[i];
-        ob.perm.resize(np);
-        for (int k = 0; k < np; k++) ob.perm[k] = k;
-        BuildCtx B{centers.data(), bmin.data(), bmax.data(), &ob.perm, &ob.nodes, {}};
-        bs.prep_ms += pc.lap("prep");
-        auto tb0 = std::chrono::steady_clock::now();
-        // non-finite centres / boxes: the GPU build does not model NaN folds
-        const bool use_gpu = s->device >= 0 && o.type != RTG_OBJ_SPHERE && all_finite &&
-                             (s->bvh_builder == RTG_BVH_GPU || (s->bvh_builder == RTG_BVH_AUTO && np >= 4096));
-        if (use_gpu) {
-            GpuBvh gb;
-            std::string err;
-            PhaseClock sub;
-            if (gpu_build_bvh(&centers[0].x, &bmin[0].x, &bmax[0].x, np, gb, err, nullptr))
-                return fail(RTG_ERR_HIP, "GPU BVH build: " + err);
-            sub.lap(" gpu_build");
-            ob.perm.resize(np);
-            parallel_chunks((size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
-                memcpy(ob.perm.data() + k0, gb.perm.as<int>() + k0, sizeof(int) * (k1 - k0));
-            });
-            // the nodes stay in the build's breadth-first order: the device records below number
-            // the interior nodes in any order (they follow child links), and only the introspection
-            // call needs the reference's pre-order (rtg_scene_object_bvh converts).  The build hands
-            // them over in HNode's layout.
-            static_assert(sizeof(HNode) == 40, "HNode = the GPU build's 40-byte node record");
-            const int nn = gb.num_nodes;
-            ob.nodes.resize(nn);
-            parallel_chunks((size_t)nn, 1 << 15, [&](int, size_t k0, size_t k1) {
-                memcpy(ob.nodes.data() + k0, gb.nodes.as<HNode>() + k0, sizeof(HNode) * (k1 - k0));
-            });
-            ob.bfs = true;
-            ob.root = nn > 0 ? 0 : -1;
-            s->bvh_gpu_objects++;
-            sub.lap(" nodes");
-        } else {
-            ob.nodes.reserve(2 * (size_t)np + 1);
-            B.finite = all_finite;
-            ob.root = construct_par(B, 0, np, 0, 0, 4);
-        }
-        const double bms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
-        s->bvh_build_ms += bms;
-        bs.median_tree_ms += pc.lap("median_tree");
-        if (getenv("RTG_BUILD_TIMING"))
-            fprintf(stderr, "[rtg] object %d: %d prims, BVH %s %.1f ms\n", i, np, use_gpu ? "gpu" : "host", bms);
+            return padc;
+        }, [](float a, float b) { return std::max(a, b); });
+}
 
-        Geometry& g = geoms[i];
-        memset(&g, 0, sizeof g);
-        g.flat_split = -1;
-        g.type = o.type;
-        g.prim_base = (int)tris.size();
-        g.nprims = np;
-        g.num_textures = o.num_textures;
-        g.textures[0] = o.textures[0];
-        g.textures[1] = o.textures[1];
-        g.texture_offset = (o.type == RTG_OBJ_MESH) ? o.texture_offset : 0;
-        g.smooth = o.smooth;
-        if (o.type == RTG_OBJ_SPHERE) {
-            V3 c = verts[o.center - 1];
-            g.center[0] = c.x; g.center[1] = c.y; g.center[2] = c.z;
-            g.radius = o.radius;
-            g.center_index = o.center;
-        }
-        // primitives in BVH order (chunks of positions in parallel)
-        const size_t pbase = tris.size();
-        tris.resize(pbase + np);
-        primidx.resize(pbase + np);
-        s->orig_prim.resize(pbase + np);
+// What the SAH thread of one object owns: the binned-SAH recursion over the triangles in parse order,
+// the collapse to 4-wide nodes (leaf refs from tri_base0, the object's first traversal-order
+// triangle) and the triangles' records in that order (p2.yzw, which need the reference tree, are
+// filled after the join).  The thread touches only this struct and the const inputs of start().
+struct SahBuild {
+    hvec<SahRec> rec_buf, tmp;
+    hvec<int> idx;
+    std::vector<SahNode2> bn;            // host build (the GPU build collapses on the device)
+    hvec<Node4> nodes;
+    hvec<TriGeom> tris;
+    bool root_interior = false;
+    uint64_t hash = 0, bnodes = 0;
+    std::exception_ptr err;
+    ScopedThread th;                     // last: the thread never outlives the buffers above
+
+    // device >= 0: tree, collapse and hash on that device
+    void start(const std::vector<V3>& verts, const ObjWork& w, int device, int tri_base0) {
+        const int np = w.np;
+        const bool gpu = device >= 0;
+        rec_buf.resize(np);
+        if (!gpu) tmp.resize(np);
+        idx.resize(np);
         parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
-          for (size_t k = k0; k < k1; k++) {
-            const int f = ob.perm[k];
-            TriGeom tg;
-            int4 pi;
-            if (o.type == RTG_OBJ_SPHERE) {
-                memset(&tg, 0, sizeof tg);
-                pi = make_int4(o.center, 0, 0, 0);
-            } else {
-                tg = tri_geom(verts, pv, (size_t)f);
-                const int smooth = (o.type == RTG_OBJ_TRIANGLE) ? 1 : o.smooth;   // Shape.cpp:262-276 quirk
-                pi = make_int4(pv[3 * f], pv[3 * f + 1], pv[3 * f + 2], smooth);
+            for (size_t f = k0; f < k1; f++) {
+                SahRec& q = rec_buf[f];
+                for (int z = 0; z < 3; z++) { q.lo[z] = comp(w.bmin[f], z); q.hi[z] = comp(w.bmax[f], z); }
+                q.idx = (int)f;
+                q.pad_ = 0;
             }
-            tris[pbase + k] = tg;
-            primidx[pbase + k] = pi;
-            s->orig_prim[pbase + k] = f;
-          }
         });
-        const float pad = obj_pad;
-        g.prune_pad = pad;
-        // linearise interior nodes (in the tree's node order) into child-box nodes: per-chunk
-        // interior counts, then every chunk numbers its own interior nodes from its offset
-        const hvec<HNode>& hn = ob.nodes;
-        hvec<int> dev_index(hn.size());
-        const int node_base = (int)dnodes.size();
-        std::vector<int> chunk_cnt(build_threads() + 1, 0);
-        const int TN = parallel_chunks(hn.size(), 1 << 15, [&](int ch, size_t k0, size_t k1) {
-            int c = 0;
-            for (size_t k = k0; k < k1; k++) c += (hn[k].left >= 0 || hn[k].right >= 0);
-            chunk_cnt[ch] = c;
-        });
-        std::vector<int> chunk_off(TN + 1, node_base);
-        for (int c = 0; c < TN; c++) chunk_off[c + 1] = chunk_off[c] + chunk_cnt[c];
-        const int cnt = chunk_off[TN] - node_base;
-        parallel_chunks(hn.size(), 1 << 15, [&](int ch, size_t k0, size_t k1) {
-            int at = chunk_off[ch];
-            for (size_t k = k0; k < k1; k++) dev_index[k] = (hn[k].left >= 0 || hn[k].right >= 0) ? at++ : -1;
-        });
-        dnodes.resize(node_base + cnt);
-        parallel_chunks(hn.size(), 1 << 15, [&](int, size_t k0, size_t k1) {
-          for (size_t k = k0; k < k1; k++) {
-            if (dev_index[k] < 0) continue;
-            Node nd;
-            float box[2][6];
-            int ref[2], count[2];
-            int ch[2] = {hn[k].left, hn[k].right};
-            for (int q = 0; q < 2; q++) {
-                int c = ch[q];
-                for (int z = 0; z < 6; z++) box[q][z] = 0.0f;
-                if (c < 0) { ref[q] = 0; count[q] = -1; continue; }
-                const HNode& cn = hn[c];
-                for (int z = 0; z < 3; z++) { box[q][z] = cn.mn[z]; box[q][3 + z] = cn.mx[z]; }
-                if (cn.left < 0 && cn.right < 0) {
-                    int len = cn.end - cn.start;
-                    ref[q] = g.prim_base + cn.start;
-                    count[q] = len > 0 ? len : -1;
-                } else {
-                    ref[q] = dev_index[c];
-                    count[q] = 0;
-                }
+        if (!gpu) bn.reserve(2 * (size_t)np / kSahMaxLeaf + 16);
+        th.t = std::thread([this, &verts, &pv = w.pv, np, device, tri_base0, obj_pad = w.obj_pad] {
+            try {
+                run(verts, pv, np, device, tri_base0, obj_pad);
+            } catch (...) {
+                err = std::current_exception();
             }
-            nd.a = make_float4(box[0][0], box[0][1], box[0][2], box[0][3]);
-            nd.b = make_float4(box[0][4], box[0][5], box[1][0], box[1][1]);
-            nd.c = make_float4(box[1][2], box[1][3], box[1][4], box[1][5]);
-            nd.d = make_int4(ref[0], ref[1], count[0], count[1]);
-            dnodes[dev_index[k]] = nd;
-          }
         });
-        // reference leaf of every position: its first position (tie order) and the box of the
-        // interior node above it, which gates it (none under the root: closest_hit tests the root)
-        gates.resize(6 * (size_t)(g.prim_base + np));
-        parallel_chunks(6 * (size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
-            std::fill(gates.begin() + 6 * (size_t)g.prim_base + k0, gates.begin() + 6 * (size_t)g.prim_base + k1, 0.0f);
-        });
-        std::vector<int> leaf_start(np, 0);
-        std::vector<char> gated(np, 0);
-        if (ob.root >= 0 && hn[ob.root].left < 0 && hn[ob.root].right < 0)
-            for (int k = hn[ob.root].start; k < hn[ob.root].end; k++) leaf_start[k] = g.prim_base + hn[ob.root].start;
-        parallel_chunks(hn.size(), 1 << 15, [&](int, size_t n0, size_t n1) {   // a leaf has one parent
-          for (size_t n2 = n0; n2 < n1; n2++) {
-            const int ch[2] = {hn[n2].left, hn[n2].right};
-            for (int c : ch) {
-                if (c < 0 || hn[c].left >= 0 || hn[c].right >= 0) continue;
-                for (int k = hn[c].start; k < hn[c].end; k++) {
-                    leaf_start[k] = g.prim_base + hn[c].start;
-                    gated[k] = (int)n2 != ob.root;
-                    for (int z = 0; z < 3; z++) {
-                        gates[6 * (size_t)(g.prim_base + k) + z] = hn[n2].mn[z];
-                        gates[6 * (size_t)(g.prim_base + k) + 3 + z] = hn[n2].mx[z];
-                    }
-                }
-            }
-          }
-        });
-        if (np <= kFlatMaxPrims) {                  // small meshes: kept for the flat group
-            pos_leaf.resize(std::max(pos_leaf.size(), (size_t)(g.prim_base + np)), 0);
-            pos_gated.resize(std::max(pos_gated.size(), (size_t)(g.prim_base + np)), 0);
-            for (int k = 0; k < np; k++) { pos_leaf[g.prim_base + k] = leaf_start[k]; pos_gated[g.prim_base + k] = gated[k]; }
-        }
-        // traversal tree (SAH, 4-wide) of a triangle object with an interior reference root and
-        // finite primitives (its boxes must bound every candidate; NaN / inf objects keep the
-        // reference-tree walk)
-        g.sah_base = -1;
-        const bool sah_ok = sah_try && ob.root >= 0 && (hn[ob.root].left >= 0 || hn[ob.root].right >= 0);
-        bs.records_ms += pc.lap("records");
-        PhaseClock sub;
-        // The last object's reference-tree records are final now: a helper thread uploads them while
-        // this one finishes the traversal tree and the top level (joined before the remaining uploads;
-        // nothing below writes these arrays).  Dragon1m: ~7-10 ms of host-to-device copies.
-        if (s->device >= 0 && i == d->num_objects - 1 && sah_thread.joinable()) {
-            early_thread = std::thread([&, dev = s->device] {
-                if (hipSetDevice(dev) != hipSuccess) { early_rc = RTG_ERR_HIP; early_err = "hipSetDevice"; return; }
-                int rc2;
-                if ((rc2 = upload(s->d_nodes, dnodes)) || (rc2 = upload(s->d_gates, gates)) || (rc2 = upload(s->d_tris, tris)) ||
-                    (rc2 = upload(s->d_primidx, primidx)) || (rc2 = upload(s->d_origprim, s->orig_prim)) ||
-                    (rc2 = upload(s->d_vnormals, s->vnormals))) {
-                    early_rc = rc2;
-                    early_err = rtg_last_error();
-                }
-            });
-            early_upload = true;
-            sub.lap(" early_upload start");
-        }
-        if (sah_thread.joinable()) sah_thread.join();
-        if (sah_err) std::rethrow_exception(sah_err);
-        sub.lap(" sah_join_wait");
-        if (sah_ok) {
-            bs.traversal_nodes += sah_bnodes;
-            bs.traversal_hash += sah_hash;
-            if (sah_gpu) bs.sah_gpu_objects++;
-            if (sah_root_interior) {
-                // SAH leaf order: face index -> reference position (inverse of the median tree's
-                // perm); the thread's records get their reference position, leaf and gate flag
-                std::vector<int> pos_of(np);
-                parallel_chunks((size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
-                    for (size_t k = k0; k < k1; k++) pos_of[ob.perm[k]] = (int)k;
-                });
-                const int tri_base = (int)stris.size();
-                if (tri_base != tri_base0) return fail(RTG_ERR_UNSUPPORTED, "internal: traversal-tree triangle base");
-                parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
-                    for (size_t k = k0; k < k1; k++) {
-                        const int r = pos_of[sah_idx[k]];
-                        TriGeom& t = sah_tris[k];
-                        const int pos = g.prim_base + r, gt = gated[r];
-                        memcpy(&t.p2.y, &pos, 4);
-                        memcpy(&t.p2.z, &leaf_start[r], 4);
-                        memcpy(&t.p2.w, &gt, 4);
-                    }
-                });
-                if (stris.empty()) stris = std::move(sah_tris);
-                else stris.insert(stris.end(), sah_tris.begin(), sah_tris.end());
-                sub.lap(" stris");
-                // the thread's nodes, interior refs shifted to this mesh's first node
-                const size_t first = snodes.size();
-                const size_t nsub = sah_nodes.size();
-                const int off = (int)first;
-                if (first == 0) {
-                    snodes = std::move(sah_nodes);
-                } else {
-                    snodes.resize(first + sah_nodes.size());
-                    parallel_chunks(sah_nodes.size(), 1 << 15, [&](int, size_t k0, size_t k1) {
-                        for (size_t k = k0; k < k1; k++) {
-                            Node4 x = sah_nodes[k];
-                            if (x.info.x == 0) x.ref.x += off;
-                            if (x.info.y == 0) x.ref.y += off;
-                            if (x.info.z == 0) x.ref.z += off;
-                            if (x.info.w == 0) x.ref.w += off;
-                            snodes[first + k] = x;
-                        }
-                    });
-                }
-                g.sah_base = off;
-                sub.lap(" nodes");
-                if (nsub == 1 && np <= kFlatMaxPrims) { g.flat_first = tri_base; g.flat_count = np; }
-            }
-        }
-        bs.traversal_tree_ms += pc.lap("traversal_tree");
-        if (ob.root < 0) {
-            g.node_base = -1; g.root_leaf_start = g.prim_base; g.root_leaf_count = -1;
-        } else if (hn[ob.root].left < 0 && hn[ob.root].right < 0) {
-            int len = hn[ob.root].end - hn[ob.root].start;
-            g.node_base = -1;
-            g.root_leaf_start = g.prim_base + hn[ob.root].start;
-            g.root_leaf_count = len > 0 ? len : -1;
-        } else {
-            g.node_base = dev_index[ob.root];
-            g.root_leaf_start = 0; g.root_leaf_count = -1;
-            for (int z = 0; z < 3; z++) {
-                g.root_min[z] = hn[ob.root].mn[z]; g.root_max[z] = hn[ob.root].mx[z];
-                g.win_min[z] = std::nextafter((float)((double)g.root_min[z] - g.prune_pad), -FLT_MAX);
-                g.win_max[z] = std::nextafter((float)((double)g.root_max[z] + g.prune_pad), FLT_MAX);
-            }
-            // every mesh by default: on the dragon the 2-triangle floor is skipped by every ray going
-            // up (frame 35.9 -> 35.5 ms against meshes of >= 64 triangles only), cornell / cornell_pt
-            // lose about 1 % (profiles/history/r3_ab_flat.jsonl)
-            g.win = g.nprims >= kWinMinPrims;
-            // a reference root over two leaves (the walk always visits both: leaves carry no tested box)
-            const HNode& rn = hn[ob.root];
-            auto leaf_of = [&](int c) { return c >= 0 && hn[c].left < 0 && hn[c].right < 0 && hn[c].end > hn[c].start; };
-            if (g.sah_base < 0 && np <= kFlatMaxPrims && leaf_of(rn.left) && leaf_of(rn.right) &&
-                hn[rn.right].start == hn[rn.left].end) {
-                g.flat_first = g.prim_base + hn[rn.left].start;
-                g.flat_split = g.prim_base + hn[rn.right].start;
-                g.flat_count = hn[rn.right].end - hn[rn.left].start;
-            }
-        }
+    }
+    void join() {                        // rethrows what the thread caught
+        if (th.t.joinable()) th.t.join();
+        if (err) std::rethrow_exception(err);
     }
 
-    // top-level entries
-    std::vector<TopObject> tops(d->num_objects + d->num_instances);
+private:
+    void run(const std::vector<V3>& verts, const std::vector<int>& pv, int np, int device, int tri_base0, float obj_pad) {
+        PhaseClock tc;
+        if (device >= 0) {
+            std::string e;
+            if (hipSetDevice(device) != hipSuccess)
+                throw std::runtime_error("GPU SAH build: hipSetDevice failed");
+            auto alloc4 = [&](size_t c) { nodes.resize(c); return nodes.data(); };
+            if (gpu_build_sah(rec_buf.data(), np, tri_base0, obj_pad, alloc4, idx.data(), bnodes, hash, e))
+                throw std::runtime_error("GPU SAH build: " + e);
+            root_interior = !nodes.empty();
+            tc.lap(" sah_tree+collapse gpu (thread)");
+            if (root_interior) {
+                node4_preorder(nodes);
+                tc.lap(" node4 preorder (thread)");
+            }
+        } else {
+            sah_rec_par(rec_buf.data(), tmp.data(), 0, np, bn, sah_depth());
+            parallel_chunks((size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; k++) idx[k] = rec_buf[k].idx;
+            });
+            tc.lap(" sah_tree (thread)");
+            sah_tree_stats(bn.data(), 0, bnodes, hash);
+            root_interior = bn[0].left >= 0;
+            if (root_interior) {
+                nodes.reserve((size_t)np / 2 + 16);
+                sah_collapse_par(bn.data(), 0, tri_base0, obj_pad, nodes, 3);
+                tc.lap(" sah_collapse (thread)");
+            }
+        }
+        if (root_interior) {
+            tris.resize(np);
+            parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
+                for (size_t k = k0; k < k1; k++) tris[k] = tri_geom(verts, pv, (size_t)idx[k]);
+            });
+            tc.lap(" sah_tris (thread)");
+        }
+    }
+};
+
+// The reference's median tree of one object: on the GPU (copied into `ob`) or by construct_par.
+int build_median_tree(rtg_scene* s, const ObjWork& w, ObjBVH& ob, bool use_gpu) {
+    const int np = w.np;
+    if (use_gpu) {
+        GpuBvh gb;
+        std::string err;
+        PhaseClock sub;
+        if (gpu_build_bvh(&w.centers[0].x, &w.bmin[0].x, &w.bmax[0].x, np, gb, err, nullptr))
+            return fail(RTG_ERR_HIP, "GPU BVH build: " + err);
+        sub.lap(" gpu_build");
+        ob.perm.resize(np);
+        parallel_chunks((size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
+            memcpy(ob.perm.data() + k0, gb.perm.as<int>() + k0, sizeof(int) * (k1 - k0));
+        });
+        // the nodes stay in the build's breadth-first order: the device records below number
+        // the interior nodes in any order (they follow child links), and only the introspection
+        // call needs the reference's pre-order (rtg_scene_object_bvh converts).  The build hands
+        // them over in HNode's layout.
+        static_assert(sizeof(HNode) == 40, "HNode = the GPU build's 40-byte node record");
+        const int nn = gb.num_nodes;
+        ob.nodes.resize(nn);
+        parallel_chunks((size_t)nn, 1 << 15, [&](int, size_t k0, size_t k1) {
+            memcpy(ob.nodes.data() + k0, gb.nodes.as<HNode>() + k0, sizeof(HNode) * (k1 - k0));
+        });
+        ob.bfs = true;
+        ob.root = nn > 0 ? 0 : -1;
+        s->bvh_gpu_objects++;
+        sub.lap(" nodes");
+    } else {
+        BuildCtx B{w.centers.data(), w.bmin.data(), w.bmax.data(), &ob.perm, &ob.nodes, {}};
+        ob.nodes.reserve(2 * (size_t)np + 1);
+        B.finite = w.all_finite;
+        ob.root = construct_par(B, 0, np, 0, 0, 4);
+    }
+    return RTG_OK;
+}
+
+// Reference records: the object's Geometry and its primitives in BVH order (tris, primidx, orig_prim).
+void reference_primitives(rtg_scene* s, SceneArrays& A, const ObjWork& w, const ObjBVH& ob, Geometry& g) {
+    const rtg_object_desc& o = w.o;
+    const std::vector<V3>& verts = A.verts;
+    const std::vector<int>& pv = w.pv;
+    const int np = w.np;
+    hvec<TriGeom>& tris = A.tris;
+    hvec<int4>& primidx = A.primidx;
+    memset(&g, 0, sizeof g);
+    g.flat_split = -1;
+    g.type = o.type;
+    g.prim_base = (int)tris.size();
+    g.nprims = np;
+    g.num_textures = o.num_textures;
+    g.textures[0] = o.textures[0];
+    g.textures[1] = o.textures[1];
+    g.texture_offset = (o.type == RTG_OBJ_MESH) ? o.texture_offset : 0;
+    g.smooth = o.smooth;
+    if (o.type == RTG_OBJ_SPHERE) {
+        V3 c = verts[o.center - 1];
+        g.center[0] = c.x; g.center[1] = c.y; g.center[2] = c.z;
+        g.radius = o.radius;
+        g.center_index = o.center;
+    }
+    // primitives in BVH order (chunks of positions in parallel)
+    const size_t pbase = tris.size();
+    tris.resize(pbase + np);
+    primidx.resize(pbase + np);
+    s->orig_prim.resize(pbase + np);
+    parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
+      for (size_t k = k0; k < k1; k++) {
+        const int f = ob.perm[k];
+        TriGeom tg;
+        int4 pi;
+        if (o.type == RTG_OBJ_SPHERE) {
+            memset(&tg, 0, sizeof tg);
+            pi = make_int4(o.center, 0, 0, 0);
+        } else {
+            tg = tri_geom(verts, pv, (size_t)f);
+            const int smooth = (o.type == RTG_OBJ_TRIANGLE) ? 1 : o.smooth;   // Shape.cpp:262-276 quirk
+            pi = make_int4(pv[3 * f], pv[3 * f + 1], pv[3 * f + 2], smooth);
+        }
+        tris[pbase + k] = tg;
+        primidx[pbase + k] = pi;
+        s->orig_prim[pbase + k] = f;
+      }
+    });
+    g.prune_pad = w.obj_pad;
+}
+
+// Reference records: the interior nodes (in the tree's node order) linearised into child-box
+// nodes: per-chunk interior counts, then every chunk numbers its own interior nodes from its offset.
+void linearise_nodes(hvec<Node>& dnodes, ObjWork& w, const ObjBVH& ob, const Geometry& g) {
+    const hvec<HNode>& hn = ob.nodes;
+    hvec<int>& dev_index = w.dev_index;
+    dev_index.resize(hn.size());
+    const int node_base = (int)dnodes.size();
+    std::vector<int> chunk_cnt(build_threads() + 1, 0);
+    const int TN = parallel_chunks(hn.size(), 1 << 15, [&](int ch, size_t k0, size_t k1) {
+        int c = 0;
+        for (size_t k = k0; k < k1; k++) c += !is_leaf(hn[k]);
+        chunk_cnt[ch] = c;
+    });
+    std::vector<int> chunk_off(TN + 1, node_base);
+    for (int c = 0; c < TN; c++) chunk_off[c + 1] = chunk_off[c] + chunk_cnt[c];
+    const int cnt = chunk_off[TN] - node_base;
+    parallel_chunks(hn.size(), 1 << 15, [&](int ch, size_t k0, size_t k1) {
+        int at = chunk_off[ch];
+        for (size_t k = k0; k < k1; k++) dev_index[k] = !is_leaf(hn[k]) ? at++ : -1;
+    });
+    dnodes.resize(node_base + cnt);
+    parallel_chunks(hn.size(), 1 << 15, [&](int, size_t k0, size_t k1) {
+      for (size_t k = k0; k < k1; k++) {
+        if (dev_index[k] < 0) continue;
+        Node nd;
+        float box[2][6];
+        int ref[2], count[2];
+        int ch[2] = {hn[k].left, hn[k].right};
+        for (int q = 0; q < 2; q++) {
+            int c = ch[q];
+            for (int z = 0; z < 6; z++) box[q][z] = 0.0f;
+            if (c < 0) { ref[q] = 0; count[q] = -1; continue; }
+            const HNode& cn = hn[c];
+            for (int z = 0; z < 3; z++) { box[q][z] = cn.mn[z]; box[q][3 + z] = cn.mx[z]; }
+            if (is_leaf(cn)) {
+                int len = cn.end - cn.start;
+                ref[q] = g.prim_base + cn.start;
+                count[q] = len > 0 ? len : -1;
+            } else {
+                ref[q] = dev_index[c];
+                count[q] = 0;
+            }
+        }
+        nd.a = make_float4(box[0][0], box[0][1], box[0][2], box[0][3]);
+        nd.b = make_float4(box[0][4], box[0][5], box[1][0], box[1][1]);
+        nd.c = make_float4(box[1][2], box[1][3], box[1][4], box[1][5]);
+        nd.d = make_int4(ref[0], ref[1], count[0], count[1]);
+        dnodes[dev_index[k]] = nd;
+      }
+    });
+}
+
+// Reference records: the reference leaf of every position: its first position (tie order) and the
+// box of the interior node above it, which gates it (none under the root: closest_hit tests the
+// root); the rows of a small mesh are kept in pos_leaf / pos_gated for the flat group.
+void leaf_gates(SceneArrays& A, ObjWork& w, const ObjBVH& ob, const Geometry& g) {
+    const int np = w.np;
+    const hvec<HNode>& hn = ob.nodes;
+    hvec<float>& gates = A.gates;
+    std::vector<int>& leaf_start = w.leaf_start;
+    std::vector<char>& gated = w.gated;
+    gates.resize(6 * (size_t)(g.prim_base + np));
+    parallel_chunks(6 * (size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
+        std::fill(gates.begin() + 6 * (size_t)g.prim_base + k0, gates.begin() + 6 * (size_t)g.prim_base + k1, 0.0f);
+    });
+    leaf_start.assign(np, 0);
+    gated.assign(np, 0);
+    if (ob.root >= 0 && is_leaf(hn[ob.root]))
+        for (int k = hn[ob.root].start; k < hn[ob.root].end; k++) leaf_start[k] = g.prim_base + hn[ob.root].start;
+    parallel_chunks(hn.size(), 1 << 15, [&](int, size_t n0, size_t n1) {   // a leaf has one parent
+      for (size_t n2 = n0; n2 < n1; n2++) {
+        const int ch[2] = {hn[n2].left, hn[n2].right};
+        for (int c : ch) {
+            if (c < 0 || !is_leaf(hn[c])) continue;
+            for (int k = hn[c].start; k < hn[c].end; k++) {
+                leaf_start[k] = g.prim_base + hn[c].start;
+                gated[k] = (int)n2 != ob.root;
+                for (int z = 0; z < 3; z++) {
+                    gates[6 * (size_t)(g.prim_base + k) + z] = hn[n2].mn[z];
+                    gates[6 * (size_t)(g.prim_base + k) + 3 + z] = hn[n2].mx[z];
+                }
+            }
+        }
+      }
+    });
+    if (np <= kFlatMaxPrims) {                  // small meshes: kept for the flat group
+        std::vector<int>& pos_leaf = A.pos_leaf;
+        std::vector<char>& pos_gated = A.pos_gated;
+        pos_leaf.resize(std::max(pos_leaf.size(), (size_t)(g.prim_base + np)), 0);
+        pos_gated.resize(std::max(pos_gated.size(), (size_t)(g.prim_base + np)), 0);
+        for (int k = 0; k < np; k++) { pos_leaf[g.prim_base + k] = leaf_start[k]; pos_gated[g.prim_base + k] = gated[k]; }
+    }
+}
+
+// Traversal-tree merge: the SAH thread's triangles and nodes are appended to the scene's (stris,
+// snodes), and the Geometry points at them.
+int merge_traversal_tree(hvec<TriGeom>& stris, hvec<Node4>& snodes, const ObjWork& w, const ObjBVH& ob, SahBuild& sah,
+                         int tri_base0, Geometry& g, PhaseClock& sub) {
+    const int np = w.np;
+    // SAH leaf order: face index -> reference position (inverse of the median tree's
+    // perm); the thread's records get their reference position, leaf and gate flag
+    std::vector<int> pos_of(np);
+    parallel_chunks((size_t)np, 1 << 16, [&](int, size_t k0, size_t k1) {
+        for (size_t k = k0; k < k1; k++) pos_of[ob.perm[k]] = (int)k;
+    });
+    const int tri_base = (int)stris.size();
+    if (tri_base != tri_base0) return fail(RTG_ERR_UNSUPPORTED, "internal: traversal-tree triangle base");
+    parallel_chunks((size_t)np, 1 << 14, [&](int, size_t k0, size_t k1) {
+        for (size_t k = k0; k < k1; k++) {
+            const int r = pos_of[sah.idx[k]];
+            set_tri_ref(sah.tris[k], g.prim_base + r, w.leaf_start[r], w.gated[r]);
+        }
+    });
+    if (stris.empty()) stris = std::move(sah.tris);
+    else stris.insert(stris.end(), sah.tris.begin(), sah.tris.end());
+    sub.lap(" stris");
+    // the thread's nodes, interior refs shifted to this mesh's first node
+    hvec<Node4>& sah_nodes = sah.nodes;
+    const size_t first = snodes.size();
+    const size_t nsub = sah_nodes.size();
+    const int off = (int)first;
+    if (first == 0) {
+        snodes = std::move(sah_nodes);
+    } else {
+        snodes.resize(first + sah_nodes.size());
+        parallel_chunks(sah_nodes.size(), 1 << 15, [&](int, size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; k++) {
+                Node4 x = sah_nodes[k];
+                if (x.info.x == 0) x.ref.x += off;
+                if (x.info.y == 0) x.ref.y += off;
+                if (x.info.z == 0) x.ref.z += off;
+                if (x.info.w == 0) x.ref.w += off;
+                snodes[first + k] = x;
+            }
+        });
+    }
+    g.sah_base = off;
+    sub.lap(" nodes");
+    if (nsub == 1 && np <= kFlatMaxPrims) { g.flat_first = tri_base; g.flat_count = np; }
+    return RTG_OK;
+}
+
+// Root summary: node_base, the root leaf, the window and the flat_* fields of the Geometry.
+void root_summary(const ObjWork& w, const ObjBVH& ob, Geometry& g) {
+    const int np = w.np;
+    const hvec<HNode>& hn = ob.nodes;
+    const hvec<int>& dev_index = w.dev_index;
+    if (ob.root < 0) {
+        g.node_base = -1; g.root_leaf_start = g.prim_base; g.root_leaf_count = -1;
+    } else if (is_leaf(hn[ob.root])) {
+        int len = hn[ob.root].end - hn[ob.root].start;
+        g.node_base = -1;
+        g.root_leaf_start = g.prim_base + hn[ob.root].start;
+        g.root_leaf_count = len > 0 ? len : -1;
+    } else {
+        g.node_base = dev_index[ob.root];
+        g.root_leaf_start = 0; g.root_leaf_count = -1;
+        for (int z = 0; z < 3; z++) {
+            g.root_min[z] = hn[ob.root].mn[z]; g.root_max[z] = hn[ob.root].mx[z];
+            g.win_min[z] = std::nextafter((float)((double)g.root_min[z] - g.prune_pad), -FLT_MAX);
+            g.win_max[z] = std::nextafter((float)((double)g.root_max[z] + g.prune_pad), FLT_MAX);
+        }
+        // every mesh by default: on the dragon the 2-triangle floor is skipped by every ray going
+        // up (frame 35.9 -> 35.5 ms against meshes of >= 64 triangles only), cornell / cornell_pt
+        // lose about 1 % (profiles/history/r3_ab_flat.jsonl)
+        g.win = g.nprims >= kWinMinPrims;
+        // a reference root over two leaves (the walk always visits both: leaves carry no tested box)
+        const HNode& rn = hn[ob.root];
+        auto leaf_of = [&](int c) { return c >= 0 && is_leaf(hn[c]) && hn[c].end > hn[c].start; };
+        if (g.sah_base < 0 && np <= kFlatMaxPrims && leaf_of(rn.left) && leaf_of(rn.right) &&
+            hn[rn.right].start == hn[rn.left].end) {
+            g.flat_first = g.prim_base + hn[rn.left].start;
+            g.flat_split = g.prim_base + hn[rn.right].start;
+            g.flat_count = hn[rn.right].end - hn[rn.left].start;
+        }
+    }
+}
+
+// One object of the per-object traversal build: its boxes, the SAH thread, the reference tree and its
+// records, the traversal-tree merge and the root summary, with the build's laps.
+int build_object(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A, int i, PhaseClock& pc) {
+    rtg_build_stats& bs = s->bst;
+    ObjWork w{d->objects[i], A.prims[i], (int)(A.prims[i].size() / 3)};
+    const rtg_object_desc& o = w.o;
+    const int np = w.np;
+    primitive_boxes(A.verts, d->intersection_test_eps, w);
+    A.geom_finite[i] = w.all_finite;
+    // traversal tree (SAH, 4-wide; below) of a triangle object with finite primitives: its
+    // binned-SAH recursion runs on its own threads, over the triangles in parse order, while the
+    // reference's median tree is built (on the GPU for large meshes); its leaves are mapped to
+    // reference positions afterwards.  Any tree shape gives the same results (the total order
+    // of candidates and the reachability gates), so it needs no reference order.
+    const bool sah_try = o.type != RTG_OBJ_SPHERE && np >= 2 && w.all_finite && s->blas_mode != 1;
+    // the traversal tree on the GPU: large meshes of a device scene (the host recursion was the
+    // long pole of scene creation, ~75-85 ms for the dragon on its thread)
+    const bool sah_gpu = s->device >= 0 && (s->bvh_builder == RTG_BVH_GPU ||
+                                            (s->bvh_builder == RTG_BVH_AUTO && np >= kSahGpuMin));
+    const int tri_base0 = (int)A.stris.size();
+    SahBuild sah;                        // after w, which its thread reads: joined before w is destroyed
+    if (sah_try) sah.start(A.verts, w, sah_gpu ? s->device : -1, tri_base0);
+    ObjBVH& ob = s->bvh[i];
+    ob.perm.resize(np);
+    for (int k = 0; k < np; k++) ob.perm[k] = k;
+    bs.prep_ms += pc.lap("prep");
+    auto tb0 = std::chrono::steady_clock::now();
+    // non-finite centres / boxes: the GPU build does not model NaN folds
+    const bool use_gpu = s->device >= 0 && o.type != RTG_OBJ_SPHERE && w.all_finite &&
+                         (s->bvh_builder == RTG_BVH_GPU || (s->bvh_builder == RTG_BVH_AUTO && np >= 4096));
+    int rc = build_median_tree(s, w, ob, use_gpu);
+    if (rc) return rc;
+    const double bms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+    s->bvh_build_ms += bms;
+    bs.median_tree_ms += pc.lap("median_tree");
+    if (getenv("RTG_BUILD_TIMING"))
+        fprintf(stderr, "[rtg] object %d: %d prims, BVH %s %.1f ms\n", i, np, use_gpu ? "gpu" : "host", bms);
+
+    Geometry& g = A.geoms[i];
+    reference_primitives(s, A, w, ob, g);
+    linearise_nodes(A.dnodes, w, ob, g);
+    leaf_gates(A, w, ob, g);
+    // traversal tree (SAH, 4-wide) of a triangle object with an interior reference root and
+    // finite primitives (its boxes must bound every candidate; NaN / inf objects keep the
+    // reference-tree walk)
+    g.sah_base = -1;
+    const bool sah_ok = sah_try && ob.root >= 0 && !is_leaf(ob.nodes[ob.root]);
+    bs.records_ms += pc.lap("records");
+    PhaseClock sub;
+    if (s->device >= 0 && i == d->num_objects - 1 && sah.th.t.joinable()) {
+        start_early_upload(s, A);
+        sub.lap(" early_upload start");
+    }
+    sah.join();
+    sub.lap(" sah_join_wait");
+    if (sah_ok) {
+        bs.traversal_nodes += sah.bnodes;
+        bs.traversal_hash += sah.hash;
+        if (sah_gpu) bs.sah_gpu_objects++;
+        if (sah.root_interior && (rc = merge_traversal_tree(A.stris, A.snodes, w, ob, sah, tri_base0, g, sub))) return rc;
+    }
+    bs.traversal_tree_ms += pc.lap("traversal_tree");
+    root_summary(w, ob, g);
+    return RTG_OK;
+}
+
+// The identity rule of a top-level entry (TopObject::ident), from its inv, blur and kind.
+int entry_ident(const TopObject& T) {
+    // identity fast path of transform_ray: rows 0-2 of inv exactly the identity with +0
+    // off-diagonal entries, and +0 blur
+    bool ident = true;
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++) {
+            float want = (c == r) ? 1.0f : 0.0f;
+            ident = ident && memcmp(&T.inv[c * 4 + r], &want, 4) == 0;
+        }
+    for (int k = 0; k < 3; k++) {
+        float z = 0.0f;
+        ident = ident && memcmp(&T.blur[k], &z, 4) == 0;
+    }
+    // A sphere whose inverse is the identity up to the signs of its zeros (compared by value) and
+    // whose blur is zero -- an untransformed sphere: glm's inverse leaves -0 entries -- takes the
+    // same fast path: for a finite ray the transformed ray equals o + 0, d + 0 in value, and the
+    // sphere test, its point and gett() give the same values (signed zeros aside, on which no
+    // outcome depends: the test compares, t > 0 is required), so the hit record is the same.
+    if (!ident && T.kind == 0) return unit_transform(T.inv, T.blur) ? 2 : 0;    // (hit_record keeps the product: transform_ray's strict)
+    return ident ? 1 : 0;
+}
+
+// Top level: the entries (objects, then instances) and their sphere test data.
+void top_level_entries(const rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
+    std::vector<TopObject>& tops = A.tops;
+    tops.resize(d->num_objects + d->num_instances);
     for (int i = 0; i < d->num_objects + d->num_instances; i++) {
         TopObject& T = tops[i];
         memset(&T, 0, sizeof T);
@@ -1930,51 +2111,93 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
             T.geom = in.base_object;
             T.is_instance = 1;
         }
-        // identity fast path of transform_ray: rows 0-2 of inv exactly the identity with +0
-        // off-diagonal entries, and +0 blur
-        bool ident = true;
-        for (int c = 0; c < 4; c++)
-            for (int r = 0; r < 3; r++) {
-                float want = (c == r) ? 1.0f : 0.0f;
-                ident = ident && memcmp(&T.inv[c * 4 + r], &want, 4) == 0;
-            }
-        for (int k = 0; k < 3; k++) {
-            float z = 0.0f;
-            ident = ident && memcmp(&T.blur[k], &z, 4) == 0;
-        }
-        // A sphere whose inverse is the identity up to the signs of its zeros (compared by value) and
-        // whose blur is zero -- an untransformed sphere: glm's inverse leaves -0 entries -- takes the
-        // same fast path: for a finite ray the transformed ray equals o + 0, d + 0 in value, and the
-        // sphere test, its point and gett() give the same values (signed zeros aside, on which no
-        // outcome depends: the test compares, t > 0 is required), so the hit record is the same.
-        if (!ident && T.kind == 0) {
-            bool unit = true;
-            for (int c = 0; c < 4; c++)
-                for (int r = 0; r < 3; r++) unit = unit && T.inv[c * 4 + r] == (c == r ? 1.0f : 0.0f);
-            for (int k = 0; k < 3; k++) unit = unit && T.blur[k] == 0.0f;
-            T.ident = unit ? 2 : 0;    // (hit_record keeps the product: transform_ray's strict)
-        } else {
-            T.ident = ident ? 1 : 0;
-        }
+        T.ident = entry_ident(T);
     }
 
-    std::vector<SphereEnt> tsph(tops.size());
+    std::vector<SphereEnt>& tsph = A.tsph;
+    tsph.resize(tops.size());
     for (size_t i = 0; i < tops.size(); i++) {
         SphereEnt& S = tsph[i];
         memset(&S, 0, sizeof S);
         S.prim = -1;
         if (tops[i].kind == 0) {
-            const Geometry& g = geoms[tops[i].geom];
+            const Geometry& g = A.geoms[tops[i].geom];
             S.c = make_float4(g.center[0], g.center[1], g.center[2], g.radius);
             S.prim = g.nprims > 0 ? g.prim_base : -1;
         }
     }
-    // world boxes of the transformed entries: the object loop skips such an entry, before its ray
-    // transform, for a lane whose ray line misses the box (closest_hit).  (Round 5 measured every entry
-    // with a world box and, for axis-aligned ones, the top-level BVH's distance pruning -- behind the
-    // origin / beyond the winner so far -- in the object loop: dragon 30.1 -> 31.5, cornell_pt 300 ->
-    // 311 ms per frame; not kept.)
-    for (int i = 0; i < d->num_objects + d->num_instances; i++) {
+}
+
+// the bounding sphere (TopObject::bsph): centre c0 = M (root box middle), radius the largest
+// distance of a triangle corner through the model matrix (double; one parallel pass, no storage),
+// then the blur sweep (centre + blur / 2, radius + |blur| / 2), the eps overhang through the
+// matrix (Frobenius norm) and the world box's margin.  The device test adds 3e-5 |oc|^2
+// (squared) for its own rounding and the object-space line's (far origins: a skipped line has
+// |oc| > r, so that slack is >= 1e-5 |oc|, above the transform's ~2e-7 cond |o|); taken only for a
+// well-conditioned matrix and a sphere of at most 60 % of the box's volume.
+void entry_bounding_sphere(TopObject& T, const Mat4& M, const HNode& rt, const Geometry& gg, const hvec<TriGeom>& tris) {
+    T.bsph = 0;
+    if (T.wbox && T.kind == 1 && gg.nprims > 0 && gg.prim_base + gg.nprims <= (int)tris.size()) {
+        double fro = 0.0, fri = 0.0;
+        for (int c = 0; c < 3; c++)
+            for (int r = 0; r < 3; r++) {
+                fro += (double)M.c[c][r] * M.c[c][r];
+                fri += (double)T.inv[c * 4 + r] * T.inv[c * 4 + r];
+            }
+        fro = std::sqrt(fro); fri = std::sqrt(fri);
+        if (std::isfinite(fro) && std::isfinite(fri) && fro * fri <= 6.0) {     // 3 for a similarity
+            double c0[3];
+            const double m[3] = {0.5 * ((double)rt.mn[0] + rt.mx[0]), 0.5 * ((double)rt.mn[1] + rt.mx[1]),
+                                 0.5 * ((double)rt.mn[2] + rt.mx[2])};
+            for (int r = 0; r < 3; r++) {
+                c0[r] = (double)M.c[0][r] * m[0] + (double)M.c[1][r] * m[1] + (double)M.c[2][r] * m[2] + (double)M.c[3][r];
+            }
+            const double r2 = chunk_reduce<double>((size_t)gg.nprims, 65536, 0.0, [&](size_t b0, size_t b1) {
+                double mx2 = 0.0;
+                for (size_t k = (size_t)gg.prim_base + b0; k < (size_t)gg.prim_base + b1; k++) {
+                    const TriGeom& tg = tris[k];
+                    const double a[3] = {tg.p0.x, tg.p0.y, tg.p0.z};
+                    const double e[2][3] = {{tg.p0.w, tg.p1.x, tg.p1.y}, {tg.p1.z, tg.p1.w, tg.p2.x}};
+                    for (int q = 0; q < 3; q++) {
+                        double v[3], d2 = 0.0;
+                        for (int z = 0; z < 3; z++) v[z] = q == 0 ? a[z] : a[z] - e[q - 1][z];
+                        for (int r = 0; r < 3; r++) {
+                            const double w = (double)M.c[0][r] * v[0] + (double)M.c[1][r] * v[1] +
+                                             (double)M.c[2][r] * v[2] + (double)M.c[3][r] - c0[r];
+                            d2 += w * w;
+                        }
+                        mx2 = d2 > mx2 || d2 != d2 ? d2 : mx2;    // NaN propagates (no sphere)
+                    }
+                }
+                return mx2;
+            }, [](double mx2, double v) { return v > mx2 || v != v ? v : mx2; });
+            double bl = 0.0, scale = 0.0, ext = 0.0, vol = 1.0;
+            for (int z = 0; z < 3; z++) {
+                bl += (double)T.blur[z] * T.blur[z];
+                scale = std::max(scale, std::max(std::fabs((double)T.wlo[z]), std::fabs((double)T.whi[z])));
+                ext = std::max(ext, (double)T.whi[z] - (double)T.wlo[z]);
+                vol *= (double)T.whi[z] - (double)T.wlo[z];
+            }
+            const double rad = std::sqrt(r2) + 0.5 * std::sqrt(bl) + (double)gg.prune_pad * fro +
+                               1e-4 * (scale + ext) + 1e-6;
+            const double svol = 4.18879020478639 * rad * rad * rad;
+            if (std::isfinite(rad) && svol <= 0.6 * vol) {
+                T.bsph = 1;
+                for (int z = 0; z < 3; z++) T.bs[z] = (float)(c0[z] + 0.5 * (double)T.blur[z]);
+                T.bs[3] = std::nextafter((float)(rad * rad * (1.0 + 1e-6)), FLT_MAX);
+            }
+        }
+    }
+}
+
+// world boxes of the transformed entries: the object loop skips such an entry, before its ray
+// transform, for a lane whose ray line misses the box (closest_hit).  (Round 5 measured every entry
+// with a world box and, for axis-aligned ones, the top-level BVH's distance pruning -- behind the
+// origin / beyond the winner so far -- in the object loop: dragon 30.1 -> 31.5, cornell_pt 300 ->
+// 311 ms per frame; not kept.)
+void entry_world_bounds(const rtg_scene* s, const std::vector<Mat4>& top_model, const std::vector<Geometry>& geoms,
+                        const hvec<TriGeom>& tris, std::vector<TopObject>& tops) {
+    for (size_t i = 0; i < tops.size(); i++) {
         TopObject& T = tops[i];
         T.wbox = 0;
         const ObjBVH& ob = s->bvh[T.geom];
@@ -1989,78 +2212,18 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
             fin = fin && std::isfinite(T.wlo[z]) && std::isfinite(T.whi[z]);
         }
         T.wbox = fin ? 1 : 0;
-        // the bounding sphere (TopObject::bsph): centre c0 = M (root box middle), radius the largest
-        // distance of a triangle corner through the model matrix (double; one parallel pass, no storage),
-        // then the blur sweep (centre + blur / 2, radius + |blur| / 2), the eps overhang through the
-        // matrix (Frobenius norm) and the world box's margin.  The device test adds 3e-5 |oc|^2
-        // (squared) for its own rounding and the object-space line's (far origins: a skipped line has
-        // |oc| > r, so that slack is >= 1e-5 |oc|, above the transform's ~2e-7 cond |o|); taken only for a
-        // well-conditioned matrix and a sphere of at most 60 % of the box's volume.
-        T.bsph = 0;
-        const Geometry& gg = geoms[T.geom];
-        if (T.wbox && T.kind == 1 && gg.nprims > 0 && gg.prim_base + gg.nprims <= (int)tris.size()) {
-            const Mat4& M = top_model[i];
-            double fro = 0.0, fri = 0.0;
-            for (int c = 0; c < 3; c++)
-                for (int r = 0; r < 3; r++) {
-                    fro += (double)M.c[c][r] * M.c[c][r];
-                    fri += (double)T.inv[c * 4 + r] * T.inv[c * 4 + r];
-                }
-            fro = std::sqrt(fro); fri = std::sqrt(fri);
-            if (std::isfinite(fro) && std::isfinite(fri) && fro * fri <= 6.0) {     // 3 for a similarity
-                double c0[3];
-                const HNode& rt = ob.nodes[ob.root];
-                const double m[3] = {0.5 * ((double)rt.mn[0] + rt.mx[0]), 0.5 * ((double)rt.mn[1] + rt.mx[1]),
-                                     0.5 * ((double)rt.mn[2] + rt.mx[2])};
-                for (int r = 0; r < 3; r++) {
-                    c0[r] = (double)M.c[0][r] * m[0] + (double)M.c[1][r] * m[1] + (double)M.c[2][r] * m[2] + (double)M.c[3][r];
-                }
-                std::vector<double> part(build_threads(), 0.0);
-                parallel_chunks((size_t)gg.nprims, 65536, [&](int ch, size_t b0, size_t b1) {
-                    double mx2 = 0.0;
-                    for (size_t k = (size_t)gg.prim_base + b0; k < (size_t)gg.prim_base + b1; k++) {
-                        const TriGeom& tg = tris[k];
-                        const double a[3] = {tg.p0.x, tg.p0.y, tg.p0.z};
-                        const double e[2][3] = {{tg.p0.w, tg.p1.x, tg.p1.y}, {tg.p1.z, tg.p1.w, tg.p2.x}};
-                        for (int q = 0; q < 3; q++) {
-                            double v[3], d2 = 0.0;
-                            for (int z = 0; z < 3; z++) v[z] = q == 0 ? a[z] : a[z] - e[q - 1][z];
-                            for (int r = 0; r < 3; r++) {
-                                const double w = (double)M.c[0][r] * v[0] + (double)M.c[1][r] * v[1] +
-                                                 (double)M.c[2][r] * v[2] + (double)M.c[3][r] - c0[r];
-                                d2 += w * w;
-                            }
-                            mx2 = d2 > mx2 || d2 != d2 ? d2 : mx2;    // NaN propagates (no sphere)
-                        }
-                    }
-                    part[ch] = mx2;
-                });
-                double r2 = 0.0, bl = 0.0, scale = 0.0, ext = 0.0, vol = 1.0;
-                for (double v : part) r2 = v > r2 || v != v ? v : r2;
-                for (int z = 0; z < 3; z++) {
-                    bl += (double)T.blur[z] * T.blur[z];
-                    scale = std::max(scale, std::max(std::fabs((double)T.wlo[z]), std::fabs((double)T.whi[z])));
-                    ext = std::max(ext, (double)T.whi[z] - (double)T.wlo[z]);
-                    vol *= (double)T.whi[z] - (double)T.wlo[z];
-                }
-                const double rad = std::sqrt(r2) + 0.5 * std::sqrt(bl) + (double)gg.prune_pad * fro +
-                                   1e-4 * (scale + ext) + 1e-6;
-                const double svol = 4.18879020478639 * rad * rad * rad;
-                if (std::isfinite(rad) && svol <= 0.6 * vol) {
-                    T.bsph = 1;
-                    for (int z = 0; z < 3; z++) T.bs[z] = (float)(c0[z] + 0.5 * (double)T.blur[z]);
-                    T.bs[3] = std::nextafter((float)(rad * rad * (1.0 + 1e-6)), FLT_MAX);
-                }
-            }
-        }
+        entry_bounding_sphere(T, top_model[i], r, geoms[T.geom], tris);
     }
+}
 
-    // top-level BVH over the entries (objects, then instances): replaces the reference's linear
-    // object loop (src/Helper.cpp:32-73) for scenes with many objects
-    std::vector<Node> tlas_nodes;
-    std::vector<int> tlas_idx;
+// top-level BVH over the entries (objects, then instances): replaces the reference's linear
+// object loop (src/Helper.cpp:32-73) for scenes with many objects
+void top_level_bvh(rtg_scene* s, SceneArrays& A) {
+    const std::vector<TopObject>& tops = A.tops;
+    const std::vector<Mat4>& top_model = A.top_model;
+    const std::vector<Geometry>& geoms = A.geoms;
     s->tlas_root = -1;
-    const int ntops = d->num_objects + d->num_instances;
+    const int ntops = (int)tops.size();
     const bool want_tlas = s->tlas_mode == 2 ? ntops >= 2 : (s->tlas_mode == 0 && ntops >= kTlasMinEntries);
     for (int z = 0; z < 3; z++) s->tlas_k[z] = 0.0f;
     if (want_tlas) {
@@ -2092,18 +2255,25 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
                     s->tlas_k[z] = std::max(s->tlas_k[z], (float)(k * 1.01));
                 }
         }
-        if (ok) s->tlas_root = build_tlas(boxes, aligned, tlas_nodes, tlas_idx);
-        s->tlas_count = s->tlas_root >= 0 ? (int)tlas_nodes.size() : 0;
+        if (ok) s->tlas_root = build_tlas(boxes, aligned, A.tlas_nodes, A.tlas_idx);
+        s->tlas_count = s->tlas_root >= 0 ? (int)A.tlas_nodes.size() : 0;
     }
+}
 
-    // the flat group (GroupEnt, closest_hit), linear-loop scenes only.  (An untransformed object's glm
-    // inverse is the identity with signed zeros, so TopObject::ident -- +0 entries only -- is rarely set;
-    // the group asks only that its members share one transform.)
-    std::vector<TriGeom> gtris;
-    std::vector<GroupEnt> gents;
+// the flat group (GroupEnt, closest_hit), linear-loop scenes only.  (An untransformed object's glm
+// inverse is the identity with signed zeros, so TopObject::ident -- +0 entries only -- is rarely set;
+// the group asks only that its members share one transform.)
+void flat_group(rtg_scene* s, SceneArrays& A) {
+    std::vector<TopObject>& tops = A.tops;
+    const hvec<TriGeom>& tris = A.tris;
+    const std::vector<int>& pos_leaf = A.pos_leaf;
+    const std::vector<char>& pos_gated = A.pos_gated;
+    std::vector<TriGeom>& gtris = A.gtris;
+    std::vector<GroupEnt>& gents = A.gents;
+    const int ntops = (int)tops.size();
     for (int i = 0; i < ntops && s->tlas_root < 0; i++) {
         TopObject& T = tops[i];
-        const Geometry& g = geoms[T.geom];
+        const Geometry& g = A.geoms[T.geom];
         if (g.type == RTG_OBJ_SPHERE) continue;
         // one transform for the whole group: the first member's inverse and blur, bit for bit
         if (!gents.empty() && (memcmp(T.inv, tops[gents[0].entry].inv, sizeof T.inv) != 0 ||
@@ -2118,14 +2288,13 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         // candidate iff the root box and its leaf's parent box pass the exact slab test (visit_object)
         const ObjBVH& ob = s->bvh[T.geom];
         // (finite only: the gate argument needs every reference box to contain its descendants')
-        if (ob.root < 0 || !geom_finite[T.geom] || g.nprims > kFlatMaxPrims ||
+        if (ob.root < 0 || !A.geom_finite[T.geom] || g.nprims > kFlatMaxPrims ||
             g.prim_base + g.nprims > (int)pos_leaf.size())
             continue;
         std::vector<TriGeom> recs;
         for (int k = g.prim_base; k < g.prim_base + g.nprims; k++) {
             TriGeom r = tris[k];
-            const int w[3] = {k, pos_leaf[k], (int)pos_gated[k]};
-            memcpy(&r.p2.y, &w[0], 4); memcpy(&r.p2.z, &w[1], 4); memcpy(&r.p2.w, &w[2], 4);
+            set_tri_ref(r, k, pos_leaf[k], (int)pos_gated[k]);
             recs.push_back(r);
         }
         G.root_box = g.node_base >= 0;              // an interior root: its box is tested (a root leaf: none)
@@ -2142,7 +2311,7 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
     }
     s->num_gtris = (int)gtris.size();
     s->num_gents = (int)gents.size();
-    std::vector<TopObject> gtop;
+    std::vector<TopObject>& gtop = A.gtop;
     if (!gents.empty()) {
         gtop.push_back(tops[gents[0].entry]);
         // The group's transform the identity up to the signs of its zeros, zero blur (untransformed
@@ -2152,16 +2321,15 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         // by a determinant of edges and direction, neither of which involves o2, and the rest compares
         // values -- the hit record is the same (t > 0 is required, so its bits are too).
         TopObject& G0 = gtop[0];
-        bool unit = true;
-        for (int c = 0; c < 4; c++)
-            for (int r = 0; r < 3; r++) unit = unit && G0.inv[c * 4 + r] == (c == r ? 1.0f : 0.0f);
-        for (int k = 0; k < 3; k++) unit = unit && G0.blur[k] == 0.0f;
-        if (unit && !G0.ident) G0.ident = 2;
+        if (unit_transform(G0.inv, G0.blur) && !G0.ident) G0.ident = 2;
     }
-    bs.flat_group_entries = s->num_gents;
+    s->bst.flat_group_entries = s->num_gents;
+}
 
-    // materials, textures, lights
-    std::vector<MaterialDev> mats(d->num_materials);
+// Shading tables: materials, textures and texels, lights.
+void shading_tables(const rtg_scene_desc* d, SceneArrays& A) {
+    std::vector<MaterialDev>& mats = A.mats;
+    mats.resize(d->num_materials);
     for (int i = 0; i < d->num_materials; i++) {
         const rtg_material_desc& m = d->materials[i];
         MaterialDev& M = mats[i];
@@ -2171,8 +2339,9 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         M.refraction_index = m.refraction_index; M.absorption_index = m.absorption_index;
         memcpy(M.absorption, m.absorption_coeff, 12);
     }
-    std::vector<TextureDev> texs(d->num_textures);
-    std::vector<float> texels;
+    std::vector<TextureDev>& texs = A.texs;
+    std::vector<float>& texels = A.texels;
+    texs.resize(d->num_textures);
     for (int i = 0; i < d->num_textures; i++) {
         const rtg_texture_desc& t = d->textures[i];
         TextureDev& T = texs[i];
@@ -2181,7 +2350,8 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         T.texel_offset = (long long)texels.size();
         if (t.kind == RTG_TEX_IMAGE && t.texels) texels.insert(texels.end(), t.texels, t.texels + (size_t)t.width * t.height * 3);
     }
-    std::vector<LightDev> lights(d->num_lights);
+    std::vector<LightDev>& lights = A.lights;
+    lights.resize(d->num_lights);
     for (int i = 0; i < d->num_lights; i++) {
         const rtg_light_desc& l = d->lights[i];
         LightDev& L = lights[i];
@@ -2214,11 +2384,14 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
             L.v[0] = v.x; L.v[1] = v.y; L.v[2] = v.z;
         }
     }
+}
 
-    // hw7 object lights (path tracer NEE): appended after the scene's lights, in object order.
-    // World-space geometry sampled at time 0, exactly as oracle/rtg_oracle.c builds it.
-    std::vector<int> top_emit(d->num_objects + d->num_instances, -1);
-    std::vector<float> etris, ecdf;
+// hw7 object lights (path tracer NEE): appended after the scene's lights, in object order.
+// World-space geometry sampled at time 0, exactly as oracle/rtg_oracle.c builds it.
+int object_lights(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
+    const std::vector<V3>& verts = A.verts;
+    std::vector<float>&etris = A.etris, &ecdf = A.ecdf;
+    A.top_emit.assign(d->num_objects + d->num_instances, -1);
     s->num_emit = 0;
     for (int i = 0; i < d->num_objects; i++) {
         const rtg_object_desc& o = d->objects[i];
@@ -2227,7 +2400,7 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         LightDev L;
         memset(&L, 0, sizeof L);
         memcpy(L.inten, o.radiance, 12);
-        const Mat4& M = model[i];
+        const Mat4& M = A.model[i];
         if (o.type == RTG_OBJ_SPHERE) {
             L.type = kLightEmitSphere;
             V3 c = xform_point(M, verts[o.center - 1], 1.0f);
@@ -2235,7 +2408,7 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
             L.size = o.radius * vnorm(v3(M.c[0][0], M.c[0][1], M.c[0][2]));
         } else {
             L.type = kLightEmitMesh;
-            const std::vector<int>& pv = op[i].v;
+            const std::vector<int>& pv = A.prims[i];
             L.tri_first = (int)ecdf.size();
             L.tri_count = (int)(pv.size() / 3);
             float acc = 0.0f;
@@ -2249,44 +2422,40 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
             }
             L.coverage = acc;
         }
-        top_emit[i] = d->num_lights + s->num_emit;
-        lights.push_back(L);
+        A.top_emit[i] = d->num_lights + s->num_emit;
+        A.lights.push_back(L);
         s->num_emit++;
     }
+    return RTG_OK;
+}
 
-    bs.top_level_ms += pc.lap("top_level");
-    if (s->device < 0) {                // host-only build (introspection / CPU tests)
-        s->build_end = std::chrono::steady_clock::now();
-        return RTG_OK;
-    }
-    std::vector<float> vflat(d->vertices, d->vertices + 3 * (size_t)nv);
-    std::vector<float> tcflat;
-    if (d->num_texcoords > 0) tcflat.assign(d->texcoords, d->texcoords + 2 * (size_t)d->num_texcoords);
+// Upload: the early thread's join and error, then everything it did not upload.
+int upload_scene(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
+    A.vflat.assign(d->vertices, d->vertices + 3 * (size_t)d->num_vertices);
+    if (d->num_texcoords > 0) A.tcflat.assign(d->texcoords, d->texcoords + 2 * (size_t)d->num_texcoords);
     int rc;
-    if (early_thread.joinable()) early_thread.join();
-    if (early_rc != RTG_OK) return fail(early_rc, "scene upload (reference-tree records): " + early_err);
-    if (!early_upload &&
-        ((rc = upload(s->d_nodes, dnodes)) || (rc = upload(s->d_gates, gates)) || (rc = upload(s->d_tris, tris)) ||
-         (rc = upload(s->d_primidx, primidx)) || (rc = upload(s->d_origprim, s->orig_prim)) ||
-         (rc = upload(s->d_vnormals, s->vnormals))))
+    if (A.early.t.joinable()) A.early.t.join();
+    if (A.early_rc != RTG_OK) return fail(A.early_rc, "scene upload (reference-tree records): " + A.early_err);
+    if (!A.early_upload && (rc = upload_reference_records(s, A))) return rc;
+    if ((rc = upload(s->d_tops, A.tops)) || (rc = upload(s->d_geoms, A.geoms)) ||
+        (rc = upload(s->d_nodes4, A.snodes)) || (rc = upload(s->d_stris, A.stris)) ||
+        (rc = upload(s->d_vertices, A.vflat)) || (rc = upload(s->d_texcoords, A.tcflat)) ||
+        (rc = upload(s->d_materials, A.mats)) || (rc = upload(s->d_textures, A.texs)) || (rc = upload(s->d_texels, A.texels)) ||
+        (rc = upload(s->d_lights, A.lights)) ||
+        (rc = upload(s->d_topemit, A.top_emit)) || (rc = upload(s->d_etris, A.etris)) || (rc = upload(s->d_ecdf, A.ecdf)) ||
+        (rc = upload(s->d_tlas, A.tlas_nodes)) || (rc = upload(s->d_tlasidx, A.tlas_idx)) ||
+        (rc = upload(s->d_gtris, A.gtris)) || (rc = upload(s->d_gents, A.gents)) || (rc = upload(s->d_gtop, A.gtop)) ||
+        (rc = upload(s->d_tsph, A.tsph)))
         return rc;
-    if ((rc = upload(s->d_tops, tops)) || (rc = upload(s->d_geoms, geoms)) ||
-        (rc = upload(s->d_nodes4, snodes)) || (rc = upload(s->d_stris, stris)) ||
-        (rc = upload(s->d_vertices, vflat)) || (rc = upload(s->d_texcoords, tcflat)) ||
-        (rc = upload(s->d_materials, mats)) || (rc = upload(s->d_textures, texs)) || (rc = upload(s->d_texels, texels)) ||
-        (rc = upload(s->d_lights, lights)) ||
-        (rc = upload(s->d_topemit, top_emit)) || (rc = upload(s->d_etris, etris)) || (rc = upload(s->d_ecdf, ecdf)) ||
-        (rc = upload(s->d_tlas, tlas_nodes)) || (rc = upload(s->d_tlasidx, tlas_idx)) ||
-        (rc = upload(s->d_gtris, gtris)) || (rc = upload(s->d_gents, gents)) || (rc = upload(s->d_gtop, gtop)) ||
-        (rc = upload(s->d_tsph, tsph)))
-        return rc;
-    bs.upload_bytes = 0;
-    for (DBuf* b : scene_buffers(s)) bs.upload_bytes += b->used;
-    bs.upload_ms += pc.lap("upload");
+    s->bst.upload_bytes = 0;
+    for (DBuf* b : scene_buffers(s)) s->bst.upload_bytes += b->used;
+    return RTG_OK;
+}
 
-    SceneView& sv = s->sv;
+// View: the kernels' SceneView, its counts and flags derived from the descriptor.
+void derive_view(SceneView& sv, const rtg_scene_desc* d, rtg_scene* s) {
     bind_view(s);
-    sv.num_tops = (int)tops.size(); sv.num_objects = d->num_objects;
+    sv.num_tops = d->num_objects + d->num_instances; sv.num_objects = d->num_objects;
     sv.num_texcoords = d->num_texcoords;
     sv.num_materials = d->num_materials;
     sv.num_textures = d->num_textures;
@@ -2346,23 +2515,50 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
             !(m.absorption_coeff[0] == 0.0f && m.absorption_coeff[1] == 0.0f && m.absorption_coeff[2] == 0.0f))
             sv.pnt_all = 1;
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
+    PhaseClock pc;
+    rtg_build_stats& bs = s->bst;
+    // Heap-allocated so that the whole owner can go to the reaper below; until then this scope owns
+    // it, and its destructor joins the early-upload thread before any array dies.
+    auto owner = std::make_unique<SceneArrays>();
+    SceneArrays& A = *owner;
+    prepare_geometry(s, d, A);
+    bs.prep_ms += pc.lap("prep");
+
+    // BVHs and device geometry
+    A.geoms.resize(d->num_objects);
+    A.geom_finite.assign(d->num_objects, 0);
+    s->orig_prim.clear();
+    s->bvh.assign(d->num_objects, ObjBVH());
+    int rc;
+    for (int i = 0; i < d->num_objects; i++)
+        if ((rc = build_object(s, d, A, i, pc))) return rc;
+
+    top_level_entries(s, d, A);
+    entry_world_bounds(s, A.top_model, A.geoms, A.tris, A.tops);
+    top_level_bvh(s, A);
+    flat_group(s, A);
+    shading_tables(d, A);
+    if ((rc = object_lights(s, d, A))) return rc;
+    bs.top_level_ms += pc.lap("top_level");
+    if (s->device < 0) {                // host-only build (introspection / CPU tests)
+        s->build_end = std::chrono::steady_clock::now();
+        return RTG_OK;
+    }
+    if ((rc = upload_scene(s, d, A))) return rc;
+    bs.upload_ms += pc.lap("upload");
+    derive_view(s->sv, d, s);
     pc.lap("view");
     // The host copies of the uploaded records (~300 MB for a 1 M-triangle mesh) are freed by the
     // library's reaper thread (Reaper, above): unmapping them took 18-25 ms of rtg_scene_create on the
     // GPU box's host (RTG_BUILD_TIMING "release").  Only memory owned by this call goes there.
-    {
-        struct Grave {
-            hvec<Node> dnodes; hvec<Node4> snodes; hvec<TriGeom> stris, tris; hvec<float> gates; hvec<int4> primidx;
-            std::vector<V3> verts, vn; std::vector<ObjPrims> op; std::vector<float> vflat;
-        };
-        Grave* g = new (std::nothrow) Grave;
-        if (g) {
-            g->dnodes.swap(dnodes); g->snodes.swap(snodes); g->stris.swap(stris); g->tris.swap(tris);
-            g->gates.swap(gates); g->primidx.swap(primidx); g->verts.swap(verts); g->vn.swap(vn); g->op.swap(op);
-            g->vflat.swap(vflat);
-            g_reaper.submit(g, [](void* p) { delete static_cast<Grave*>(p); });
-        }
-    }
+    g_reaper.submit(owner.release(), [](void* p) { delete static_cast<SceneArrays*>(p); });
     s->build_end = std::chrono::steady_clock::now();
     return RTG_OK;
 }
@@ -2406,13 +2602,9 @@ int32_t rtg_scene_create_ex(const rtg_scene_desc* desc, int32_t device, const rt
         // thread (a 256-byte pinned copy, one empty launch), so that they overlap the
         // host part of the build (descriptor checks, primitive boxes, the traversal tree's SAH build)
         // instead of stalling the first upload.  Errors are left to the build's own calls.
-        std::thread warm;
-        struct WarmJoin {
-            std::thread& t;
-            ~WarmJoin() { if (t.joinable()) t.join(); }
-        } warm_join{warm};
+        ScopedThread warm;
         if (device >= 0)
-            warm = std::thread([device] {
+            warm.t = std::thread([device] {
                 if (hipSetDevice(device) != hipSuccess) return;
                 void* h = nullptr;
                 void* dptr = nullptr;
@@ -2432,9 +2624,9 @@ int32_t rtg_scene_create_ex(const rtg_scene_desc* desc, int32_t device, const rt
         if (getenv("RTG_BUILD_TIMING") && rc == RTG_OK)
             fprintf(stderr, "[rtg] phase %-16s %7.2f ms\n", "release",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s->build_end).count());
-        if (warm.joinable()) {
+        if (warm.t.joinable()) {
             PhaseClock wc;
-            warm.join();
+            warm.t.join();
             wc.lap("warm_join");
         }
         if (rc) {
