@@ -388,26 +388,26 @@ static v3 tex_pixel(const Tex* t, int i, int j) {
     const float* p = t->texels + ((size_t)j * t->w + i) * 3;
     return V(p[0], p[1], p[2]);
 }
-/* Texture::GetColorAtCoordinates, src/Texture.cpp:111-131 */
+/* Texture::GetColorAtCoordinates, src/Texture.cpp:111-131; a NaN coordinate gives index 0 (rtg_oracle.h) */
 static v3 tex_color(const Tex* t, float u, float v) {
     u = u - floorf(u);
     v = v - floorf(v);
     float i = u * (float)t->w;
     float j = v * (float)t->h;
-    if (t->interp == RTG_INTERP_NN) return tex_pixel(t, (int)i, (int)j);
-    int li = (int)floorf(i), lj = (int)floorf(j);
+    if (t->interp == RTG_INTERP_NN) return tex_pixel(t, i == i ? (int)i : 0, j == j ? (int)j : 0);
+    int li = i == i ? (int)floorf(i) : 0, lj = j == j ? (int)floorf(j) : 0;
     float a = i - (float)li, b = j - (float)lj;
     v3 c00 = tex_pixel(t, li, lj), c01 = tex_pixel(t, li, lj + 1);
     v3 c10 = tex_pixel(t, li + 1, lj), c11 = tex_pixel(t, li + 1, lj + 1);
     float w00 = (1 - a) * (1 - b), w01 = (1 - a) * b, w10 = a * (1 - b), w11 = a * b;
     return vadd(vadd(vadd(vmul(c00, w00), vmul(c01, w01)), vmul(c10, w10)), vmul(c11, w11));
 }
-/* Texture::GetChangeAtCoordinates, src/Texture.cpp:76-109 */
+/* Texture::GetChangeAtCoordinates, src/Texture.cpp:76-109; a NaN coordinate gives index 0 (rtg_oracle.h) */
 static v2 tex_change(const Tex* t, float u, float v) {
     u = u - floorf(u);
     v = v - floorf(v);
-    int i = (int)(u * (float)t->w);
-    int j = (int)(v * (float)t->h);
+    int i = u == u ? (int)(u * (float)t->w) : 0;
+    int j = v == v ? (int)(v * (float)t->h) : 0;
     if (i < 0) i = 0; else if (i >= t->w - 1) i = t->w - 2;
     if (j < 0) j = 0; else if (j >= t->h - 1) j = t->h - 2;
     v3 a = tex_pixel(t, i + 1, j), b = tex_pixel(t, i, j), c = tex_pixel(t, i, j + 1);
@@ -1609,7 +1609,7 @@ void orc_scene_destroy(orc_scene* s) {
 }
 
 int orc_scene_create(const rtg_scene_desc* d, orc_scene** out) {
-    if (!d || !out) return RTG_ERR_INVALID;
+    if (!d || !out || !orc_desc_valid(d)) return RTG_ERR_INVALID;
     struct orc_scene* s = (struct orc_scene*)calloc(1, sizeof *s);
     s->maxDepth = d->max_recursion_depth;
     s->shadowEps = d->shadow_ray_eps;

@@ -21,6 +21,16 @@ extern "C" {
 
 typedef struct orc_scene orc_scene;
 
+/* 1 if orc_scene_create accepts the description: the index checks of librtg's validate() (object materials
+   and texture lists, instance bases and materials, image textures without texels, environment-light and
+   background textures, the environment light itself); orc_validate.c. */
+int orc_desc_valid(const rtg_scene_desc* desc);
+/* RTG_ERR_INVALID, *out untouched, for a description that orc_desc_valid refuses (rtg_scene_create refuses
+   it too).
+   Texture lookups: the reference converts a texture coordinate to an int index (src/Texture.cpp:79-80, 118,
+   121-122).  At a sphere pole the coordinate can be NaN (acos of a ratio one ulp over 1), and that conversion
+   is undefined in C: the reference's x86 build yields INT_MIN, which GetColorAtPixel's clamp turns into
+   texel 0, and the GPU's conversion yields 0, the same texel.  The restatement converts NaN to 0. */
 int orc_scene_create(const rtg_scene_desc* desc, orc_scene** out);
 void orc_scene_destroy(orc_scene* s);
 
