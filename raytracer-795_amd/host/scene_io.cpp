@@ -456,300 +456,283 @@ struct rtgh_scene {
 
 namespace {
 
-int parse(const std::string& xml_path, rtgh_scene& sc) {
-    std::string src;
-    if (!read_file(xml_path, src)) return fail(RTG_ERR_INVALID, "cannot read " + xml_path);
-    std::string err;
-    rtgh::XmlParser xp;
-    auto root = xp.parse(src, err);
-    if (!root) return fail(RTG_ERR_INVALID, err);
-    const size_t slash = xml_path.rfind('/');
-    const std::string base = slash == std::string::npos ? "" : xml_path.substr(0, slash + 1);
+// One function per section of the reference's parser, named as rtg/scene.py names them.  What crosses sections
+// is passed in: the BRDF table, the base directory, the decoded-image cache, mesh_start (the image list is
+// sc.images).
+using Xml = rtgh::XmlElement;
 
-    // ParseSceneAttributes (src/Parser.h:17-50)
-    query_int(child_text(root.get(), "MaxRecursionDepth"), sc.max_depth);
-    scan3(child_text(root.get(), "BackgroundColor"), sc.background);
-    query_float(child_text(root.get(), "ShadowRayEpsilon"), sc.shadow_eps);
-    query_float(child_text(root.get(), "IntersectionTestEpsilon"), sc.int_eps);
+std::string trim(const std::string& s) {
+    const size_t a = s.find_first_not_of(" \t\r\n"), b = s.find_last_not_of(" \t\r\n");
+    return a == std::string::npos ? "" : s.substr(a, b - a + 1);
+}
+// the text, lowered and trimmed, starts with `word`
+bool starts_with_word(const char* text, const char* word) { return trim(lower(text)).compare(0, strlen(word), word) == 0; }
 
-    // ParseCameras (Parser.h:52-164)
-    if (const rtgh::XmlElement* ce0 = root->child("Cameras")) {
-        for (const rtgh::XmlElement* ce : ce0->all("Camera")) {
-            CamData c;
-            rtg_camera_desc& d = c.d;
-            d.left = -1; d.right = 1; d.bottom = -1; d.top = 1;
-            d.near_distance = 1.0f; d.num_samples = 1;
-            d.gaze[2] = -1; d.up[1] = 1;
-            d.left_handed = attr_prefix(ce, "handedness", "left");
-            if (ce->child("FocusDistance")) { query_float(child_text(ce, "FocusDistance"), d.focus_distance); d.is_dof = 1; }
-            if (ce->child("ApertureSize")) query_float(child_text(ce, "ApertureSize"), d.aperture_size);
-            query_int(child_text(ce, "NumSamples"), d.num_samples);
-            scan3(child_text(ce, "Position"), d.position);
-            if (ce->child("Gaze")) scan3(child_text(ce, "Gaze"), d.gaze);
-            if (ce->child("GazePoint")) {                                  // Parser.h:116-123
-                float gp[3];
-                scan3(child_text(ce, "GazePoint"), gp);
-                for (int k = 0; k < 3; k++) d.gaze[k] = gp[k] - d.position[k];
-            }
-            scan3(child_text(ce, "Up"), d.up);
-            query_float(child_text(ce, "NearDistance"), d.near_distance);
-            if (const char* r = child_text(ce, "ImageResolution")) sscanf(r, "%d %d", &d.nx, &d.ny);
-            if (const char* n = child_text(ce, "ImageName")) {
-                std::string s = n;
-                size_t a = s.find_first_not_of(" \t\r\n"), b = s.find_last_not_of(" \t\r\n");
-                c.image_name = a == std::string::npos ? "" : s.substr(a, b - a + 1);
-            }
-            if (const char* np = child_text(ce, "NearPlane")) sscanf(np, "%f %f %f %f", &d.left, &d.right, &d.bottom, &d.top);
-            if (ce->child("FovY")) {                                       // Parser.h:144-158
-                float fov = 0.0f;
-                query_float(child_text(ce, "FovY"), fov);
-                const float fovr = (float)((double)(fov * 0.5f) * (3.14159265358979323846 / (double)180.0f));
-                const float aspect = (float)d.nx / (float)d.ny;
-                const float y = (float)tan((double)fovr) * d.near_distance;
-                const float x = aspect * y;
-                d.left = -x; d.right = x; d.bottom = -y; d.top = y;
-            }
-            // hw5 <Tonemap> (pages/Page5.md:47-53; no parser code in src/): Photographic TMO
-            if (const rtgh::XmlElement* tm = ce->child("Tonemap")) {
-                const char* tmo = child_text(tm, "TMO");
-                std::string t = lower(tmo ? tmo : "photographic");
-                size_t a = t.find_first_not_of(" \t\r\n");
-                if (a != std::string::npos && t.compare(a, 12, "photographic") == 0) {
-                    c.has_tonemap = true;
-                    c.tm.tmo = RTG_TMO_PHOTOGRAPHIC;
-                    c.tm.key = 0.18f; c.tm.burn_percent = 1.0f;
-                    if (const char* o = child_text(tm, "TMOOptions")) {
-                        c.tm.key = c.tm.burn_percent = 0.0f;
-                        sscanf(o, "%f %f", &c.tm.key, &c.tm.burn_percent);
-                    }
-                    c.tm.saturation = 1.0f; c.tm.gamma = 2.2f;
-                    query_float(child_text(tm, "Saturation"), c.tm.saturation);
-                    query_float(child_text(tm, "Gamma"), c.tm.gamma);
-                }
-            }
-            // hw7 (pages/Page7.md): <Renderer>PathTracing</Renderer>, <RendererParams>
-            if (const char* r = child_text(ce, "Renderer")) {
-                std::string s = lower(r);
-                size_t a = s.find_first_not_of(" \t\r\n");
-                if (a != std::string::npos && s.compare(a, 11, "pathtracing") == 0) d.integrator = RTG_INTEGRATOR_PATH;
-            }
-            if (const char* r = child_text(ce, "RendererParams")) {
-                std::istringstream ss(lower(r));
-                std::string t;
-                while (ss >> t) {
-                    if (t == "importancesampling") d.pt_flags |= RTG_PT_IMPORTANCE;
-                    else if (t == "nexteventestimation") d.pt_flags |= RTG_PT_NEE;
-                    else if (t == "russianroulette") d.pt_flags |= RTG_PT_RUSSIAN_ROULETTE;
-                }
-            }
-            sc.cameras.push_back(c);
+// ParseSceneAttributes (src/Parser.h:17-50)
+void parse_scene_attributes(const Xml* root, rtgh_scene& sc) {
+    query_int(child_text(root, "MaxRecursionDepth"), sc.max_depth);
+    scan3(child_text(root, "BackgroundColor"), sc.background);
+    query_float(child_text(root, "ShadowRayEpsilon"), sc.shadow_eps);
+    query_float(child_text(root, "IntersectionTestEpsilon"), sc.int_eps);
+}
+
+// hw5 <Tonemap> (pages/Page5.md:47-53; no parser code in src/): Photographic TMO
+void parse_tonemap(const Xml* tm, CamData& c) {
+    const char* tmo = child_text(tm, "TMO");
+    if (!starts_with_word(tmo ? tmo : "photographic", "photographic")) return;
+    c.has_tonemap = true;
+    c.tm.tmo = RTG_TMO_PHOTOGRAPHIC;
+    c.tm.key = 0.18f; c.tm.burn_percent = 1.0f;
+    if (const char* o = child_text(tm, "TMOOptions")) {
+        c.tm.key = c.tm.burn_percent = 0.0f;
+        sscanf(o, "%f %f", &c.tm.key, &c.tm.burn_percent);
+    }
+    c.tm.saturation = 1.0f; c.tm.gamma = 2.2f;
+    query_float(child_text(tm, "Saturation"), c.tm.saturation);
+    query_float(child_text(tm, "Gamma"), c.tm.gamma);
+}
+
+// hw7 (pages/Page7.md): <Renderer>PathTracing</Renderer>, <RendererParams>
+void parse_renderer(const Xml* ce, rtg_camera_desc& d) {
+    if (const char* r = child_text(ce, "Renderer"))
+        if (starts_with_word(r, "pathtracing")) d.integrator = RTG_INTEGRATOR_PATH;
+    if (const char* r = child_text(ce, "RendererParams")) {
+        std::istringstream ss(lower(r));
+        std::string t;
+        while (ss >> t) {
+            if (t == "importancesampling") d.pt_flags |= RTG_PT_IMPORTANCE;
+            else if (t == "nexteventestimation") d.pt_flags |= RTG_PT_NEE;
+            else if (t == "russianroulette") d.pt_flags |= RTG_PT_RUSSIAN_ROULETTE;
         }
     }
+}
 
-    // ParseBRDF (Parser.h:166-302): (type, id, exponent)
-    struct Brdf { int type, id, exp; };
+// ParseCameras (Parser.h:52-164)
+void parse_cameras(const Xml* root, rtgh_scene& sc) {
+    const Xml* ce0 = root->child("Cameras");
+    if (!ce0) return;
+    for (const Xml* ce : ce0->all("Camera")) {
+        CamData c;
+        rtg_camera_desc& d = c.d;
+        d.left = -1; d.right = 1; d.bottom = -1; d.top = 1;
+        d.near_distance = 1.0f; d.num_samples = 1;
+        d.gaze[2] = -1; d.up[1] = 1;
+        d.left_handed = attr_prefix(ce, "handedness", "left");
+        if (ce->child("FocusDistance")) { query_float(child_text(ce, "FocusDistance"), d.focus_distance); d.is_dof = 1; }
+        if (ce->child("ApertureSize")) query_float(child_text(ce, "ApertureSize"), d.aperture_size);
+        query_int(child_text(ce, "NumSamples"), d.num_samples);
+        scan3(child_text(ce, "Position"), d.position);
+        if (ce->child("Gaze")) scan3(child_text(ce, "Gaze"), d.gaze);
+        if (ce->child("GazePoint")) {                                  // Parser.h:116-123
+            float gp[3];
+            scan3(child_text(ce, "GazePoint"), gp);
+            for (int k = 0; k < 3; k++) d.gaze[k] = gp[k] - d.position[k];
+        }
+        scan3(child_text(ce, "Up"), d.up);
+        query_float(child_text(ce, "NearDistance"), d.near_distance);
+        if (const char* r = child_text(ce, "ImageResolution")) sscanf(r, "%d %d", &d.nx, &d.ny);
+        if (const char* n = child_text(ce, "ImageName")) c.image_name = trim(n);
+        if (const char* np = child_text(ce, "NearPlane")) sscanf(np, "%f %f %f %f", &d.left, &d.right, &d.bottom, &d.top);
+        if (ce->child("FovY")) {                                       // Parser.h:144-158
+            float fov = 0.0f;
+            query_float(child_text(ce, "FovY"), fov);
+            const float fovr = (float)((double)(fov * 0.5f) * (3.14159265358979323846 / (double)180.0f));
+            const float aspect = (float)d.nx / (float)d.ny;
+            const float y = (float)tan((double)fovr) * d.near_distance;
+            const float x = aspect * y;
+            d.left = -x; d.right = x; d.bottom = -y; d.top = y;
+        }
+        if (const Xml* tm = ce->child("Tonemap")) parse_tonemap(tm, c);
+        parse_renderer(ce, d);
+        sc.cameras.push_back(c);
+    }
+}
+
+// ParseBRDF (Parser.h:166-302): (type, id, exponent)
+struct Brdf { int type, id, exp; };
+std::vector<Brdf> parse_brdfs(const Xml* root) {
     std::vector<Brdf> brdfs;
-    if (const rtgh::XmlElement* be = root->child("BRDFs")) {
-        for (const char* tag : {"ModifiedBlinnPhong", "OriginalBlinnPhong", "ModifiedPhong", "OriginalPhong", "TorranceSparrow"}) {
-            for (const rtgh::XmlElement* b : be->all(tag)) {
-                Brdf x{0, 0, 0};
-                attr_int(b, "id", x.id);
-                query_int(child_text(b, "Exponent"), x.exp);
-                const std::string t = tag;
-                if (t == "ModifiedBlinnPhong") x.type = attr_prefix(b, "normalized", "true") ? RTG_BRDF_MBPN : RTG_BRDF_MBP;
-                else if (t == "OriginalBlinnPhong") x.type = RTG_BRDF_OBP;
-                else if (t == "ModifiedPhong") x.type = attr_prefix(b, "normalized", "true") ? RTG_BRDF_MPN : RTG_BRDF_MP;
-                else if (t == "OriginalPhong") x.type = RTG_BRDF_OP;
-                else x.type = attr_prefix(b, "kdfresnel", "true") ? RTG_BRDF_TSF : RTG_BRDF_TS;
-                brdfs.push_back(x);
-            }
+    const Xml* be = root->child("BRDFs");
+    if (!be) return brdfs;
+    struct Kind { const char* tag; int type; const char* flag; int flagged_type; };   // flag="true" picks the variant
+    static const Kind kinds[] = {{"ModifiedBlinnPhong", RTG_BRDF_MBP, "normalized", RTG_BRDF_MBPN},
+                                 {"OriginalBlinnPhong", RTG_BRDF_OBP, nullptr, 0},
+                                 {"ModifiedPhong", RTG_BRDF_MP, "normalized", RTG_BRDF_MPN},
+                                 {"OriginalPhong", RTG_BRDF_OP, nullptr, 0},
+                                 {"TorranceSparrow", RTG_BRDF_TS, "kdfresnel", RTG_BRDF_TSF}};
+    for (const Kind& k : kinds)
+        for (const Xml* b : be->all(k.tag)) {
+            Brdf x{k.flag && attr_prefix(b, k.flag, "true") ? k.flagged_type : k.type, 0, 0};
+            attr_int(b, "id", x.id);
+            query_int(child_text(b, "Exponent"), x.exp);
+            brdfs.push_back(x);
         }
-    }
+    return brdfs;
+}
 
-    // ParseMaterials (Parser.h:304-474)
-    if (const rtgh::XmlElement* me0 = root->child("Materials")) {
-        for (const rtgh::XmlElement* me : me0->all("Material")) {
-            rtg_material_desc m{};
-            const bool degamma = attr_prefix(me, "degamma", "true");
-            int bidx = -1;
-            attr_int(me, "BRDF", bidx);
-            if (bidx != -1)
-                for (const Brdf& b : brdfs)
-                    if (b.id == bidx) { m.phong_exp = b.exp; m.brdf = b.type; }
-            scan3(child_text(me, "AmbientReflectance"), m.ambient);
-            scan3(child_text(me, "DiffuseReflectance"), m.diffuse);
-            scan3(child_text(me, "SpecularReflectance"), m.specular);
-            if (degamma)
-                for (float* v : {m.ambient, m.diffuse, m.specular})
-                    for (int k = 0; k < 3; k++) v[k] = (float)pow((double)v[k], (double)2.2f);
-            if (me->child("Roughness")) { query_float(child_text(me, "Roughness"), m.roughness); m.is_rough = 1; }
-            scan3(child_text(me, "MirrorReflectance"), m.mirror);
-            if (me->child("PhongExponent")) query_int(child_text(me, "PhongExponent"), m.phong_exp);
-            m.type = RTG_MAT_NORMAL;
-            for (const auto& a : me->attrs) {
-                if (strncmp(a.first.c_str(), "type", 4) != 0) continue;
-                const char* v = a.second.c_str();
-                if (strncmp(v, "dielectric", 10) == 0) m.type = RTG_MAT_DIELECTRIC;
-                else if (strncmp(v, "conductor", 9) == 0) m.type = RTG_MAT_CONDUCTOR;
-                else if (strncmp(v, "mirror", 6) == 0) m.type = RTG_MAT_MIRROR;
-                break;
-            }
-            query_float(child_text(me, "RefractionIndex"), m.refraction_index);
-            query_float(child_text(me, "AbsorptionIndex"), m.absorption_index);
-            scan3(child_text(me, "AbsorptionCoefficient"), m.absorption_coeff);
-            sc.materials.push_back(m);
+// ParseMaterials (Parser.h:304-474)
+void parse_materials(const Xml* root, const std::vector<Brdf>& brdfs, rtgh_scene& sc) {
+    const Xml* me0 = root->child("Materials");
+    if (!me0) return;
+    for (const Xml* me : me0->all("Material")) {
+        rtg_material_desc m{};
+        const bool degamma = attr_prefix(me, "degamma", "true");
+        int bidx = -1;
+        attr_int(me, "BRDF", bidx);
+        if (bidx != -1)
+            for (const Brdf& b : brdfs)
+                if (b.id == bidx) { m.phong_exp = b.exp; m.brdf = b.type; }
+        scan3(child_text(me, "AmbientReflectance"), m.ambient);
+        scan3(child_text(me, "DiffuseReflectance"), m.diffuse);
+        scan3(child_text(me, "SpecularReflectance"), m.specular);
+        if (degamma)
+            for (float* v : {m.ambient, m.diffuse, m.specular})
+                for (int k = 0; k < 3; k++) v[k] = (float)pow((double)v[k], (double)2.2f);
+        if (me->child("Roughness")) { query_float(child_text(me, "Roughness"), m.roughness); m.is_rough = 1; }
+        scan3(child_text(me, "MirrorReflectance"), m.mirror);
+        if (me->child("PhongExponent")) query_int(child_text(me, "PhongExponent"), m.phong_exp);
+        m.type = attr_prefix(me, "type", "dielectric") ? RTG_MAT_DIELECTRIC
+               : attr_prefix(me, "type", "conductor") ? RTG_MAT_CONDUCTOR
+               : attr_prefix(me, "type", "mirror")    ? RTG_MAT_MIRROR : RTG_MAT_NORMAL;
+        query_float(child_text(me, "RefractionIndex"), m.refraction_index);
+        query_float(child_text(me, "AbsorptionIndex"), m.absorption_index);
+        scan3(child_text(me, "AbsorptionCoefficient"), m.absorption_coeff);
+        sc.materials.push_back(m);
+    }
+}
+
+// Every image file is decoded once per parse, however many textures and lights name it.
+struct DecodedImage { std::vector<float> px; int w = 0, h = 0; };
+using ImageCache = std::map<std::string, DecodedImage>;
+int image_texels(ImageCache& cache, const std::string& path, TexData& t) {
+    auto it = cache.find(path);
+    if (it == cache.end()) {
+        DecodedImage im;
+        int rc = load_image(path, im.px, im.w, im.h);
+        if (rc) return rc;
+        it = cache.emplace(path, std::move(im)).first;
+    }
+    t.texels = it->second.px;
+    t.d.width = it->second.w;
+    t.d.height = it->second.h;
+    return RTG_OK;
+}
+
+// ParseTextures (Parser.h:476-605): fields carry over between TextureMaps
+int parse_textures(const Xml* root, const std::string& base, ImageCache& cache, rtgh_scene& sc) {
+    const Xml* te = root->child("Textures");
+    if (!te) return RTG_OK;
+    if (const Xml* ie = te->child("Images"))
+        for (const Xml* im : ie->all("Image")) sc.images.push_back(base + trim(text_of(im)));
+    bool is_image = false;
+    int image_id = 0, normalizer = 255, dm = RTG_DECAL_NONE, nc = RTG_NC_LINEAR, interp = RTG_INTERP_NN;
+    float noise_scale = 1.0f, bump = 1.0f;
+    for (const Xml* tm : te->all("TextureMap")) {
+        for (const auto& a : tm->attrs)
+            if (strncmp(a.first.c_str(), "type", 4) == 0) { is_image = strncmp(a.second.c_str(), "image", 5) == 0; break; }
+        if (tm->child("ImageId")) query_int(child_text(tm, "ImageId"), image_id);
+        if (const char* s = child_text(tm, "DecalMode")) {
+            static const std::pair<const char*, int> modes[] = {
+                {"blend_kd", RTG_DECAL_BLEND_KD}, {"replace_kd", RTG_DECAL_REPLACE_KD},
+                {"replace_all", RTG_DECAL_REPLACE_ALL}, {"bump_normal", RTG_DECAL_BUMP_NORMAL},
+                {"replace_normal", RTG_DECAL_REPLACE_NORMAL}, {"replace_background", RTG_DECAL_REPLACE_BACKGROUND}};
+            for (const auto& md : modes)
+                if (strncmp(s, md.first, strlen(md.first)) == 0) { dm = md.second; break; }
         }
-    }
-
-    // ParseTextures (Parser.h:476-605): fields carry over between TextureMaps
-    std::map<std::string, std::pair<std::vector<float>, std::pair<int, int>>> cache;
-    auto image = [&](const std::string& path, TexData& t) -> int {
-        auto it = cache.find(path);
-        if (it == cache.end()) {
-            std::vector<float> px;
-            int w = 0, h = 0;
-            int rc = load_image(path, px, w, h);
+        if (const char* s = child_text(tm, "NoiseConversion")) nc = strncmp(s, "absval", 6) == 0 ? RTG_NC_ABSVAL : RTG_NC_LINEAR;
+        if (const char* s = child_text(tm, "Interpolation")) {
+            if (strncmp(s, "nearest", 7) == 0) interp = RTG_INTERP_NN;
+            else if (strncmp(s, "bilinear", 8) == 0) interp = RTG_INTERP_BILINEAR;
+        }
+        if (tm->child("Normalizer")) query_int(child_text(tm, "Normalizer"), normalizer);
+        if (tm->child("NoiseScale")) query_float(child_text(tm, "NoiseScale"), noise_scale);
+        if (tm->child("BumpFactor")) query_float(child_text(tm, "BumpFactor"), bump);
+        TexData t;
+        t.d.decal = dm; t.d.interp = interp; t.d.normalizer = normalizer; t.d.bump_factor = bump;
+        t.d.noise_conv = nc; t.d.noise_scale = noise_scale;
+        if (is_image) {
+            t.d.kind = RTG_TEX_IMAGE;
+            t.image_id = image_id;
+            if (image_id < 1 || image_id > (int)sc.images.size()) return fail(RTG_ERR_INVALID, "TextureMap ImageId out of range");
+            int rc = image_texels(cache, sc.images[image_id - 1], t);
             if (rc) return rc;
-            it = cache.emplace(path, std::make_pair(std::move(px), std::make_pair(w, h))).first;
+        } else {
+            t.d.kind = RTG_TEX_PERLIN;
         }
-        t.texels = it->second.first;
-        t.d.width = it->second.second.first;
-        t.d.height = it->second.second.second;
-        return RTG_OK;
-    };
-    if (const rtgh::XmlElement* te = root->child("Textures")) {
-        if (const rtgh::XmlElement* ie = te->child("Images"))
-            for (const rtgh::XmlElement* im : ie->all("Image")) {
-                std::string s = text_of(im);
-                size_t a = s.find_first_not_of(" \t\r\n"), b = s.find_last_not_of(" \t\r\n");
-                sc.images.push_back(base + (a == std::string::npos ? "" : s.substr(a, b - a + 1)));
-            }
-        bool is_image = false;
-        int image_id = 0, normalizer = 255, dm = RTG_DECAL_NONE, nc = RTG_NC_LINEAR, interp = RTG_INTERP_NN;
-        float noise_scale = 1.0f, bump = 1.0f;
-        for (const rtgh::XmlElement* tm : te->all("TextureMap")) {
-            for (const auto& a : tm->attrs)
-                if (strncmp(a.first.c_str(), "type", 4) == 0) { is_image = strncmp(a.second.c_str(), "image", 5) == 0; break; }
-            if (tm->child("ImageId")) query_int(child_text(tm, "ImageId"), image_id);
-            if (const char* s = child_text(tm, "DecalMode")) {
-                static const std::pair<const char*, int> modes[] = {
-                    {"blend_kd", RTG_DECAL_BLEND_KD}, {"replace_kd", RTG_DECAL_REPLACE_KD},
-                    {"replace_all", RTG_DECAL_REPLACE_ALL}, {"bump_normal", RTG_DECAL_BUMP_NORMAL},
-                    {"replace_normal", RTG_DECAL_REPLACE_NORMAL}, {"replace_background", RTG_DECAL_REPLACE_BACKGROUND}};
-                for (const auto& md : modes)
-                    if (strncmp(s, md.first, strlen(md.first)) == 0) { dm = md.second; break; }
-            }
-            if (const char* s = child_text(tm, "NoiseConversion")) nc = strncmp(s, "absval", 6) == 0 ? RTG_NC_ABSVAL : RTG_NC_LINEAR;
-            if (const char* s = child_text(tm, "Interpolation")) {
-                if (strncmp(s, "nearest", 7) == 0) interp = RTG_INTERP_NN;
-                else if (strncmp(s, "bilinear", 8) == 0) interp = RTG_INTERP_BILINEAR;
-            }
-            if (tm->child("Normalizer")) query_int(child_text(tm, "Normalizer"), normalizer);
-            if (tm->child("NoiseScale")) query_float(child_text(tm, "NoiseScale"), noise_scale);
-            if (tm->child("BumpFactor")) query_float(child_text(tm, "BumpFactor"), bump);
-            TexData t;
-            t.d.decal = dm; t.d.interp = interp; t.d.normalizer = normalizer; t.d.bump_factor = bump;
-            t.d.noise_conv = nc; t.d.noise_scale = noise_scale;
-            if (is_image) {
-                t.d.kind = RTG_TEX_IMAGE;
-                t.image_id = image_id;
-                if (image_id < 1 || image_id > (int)sc.images.size()) return fail(RTG_ERR_INVALID, "TextureMap ImageId out of range");
-                int rc = image(sc.images[image_id - 1], t);
-                if (rc) return rc;
-            } else {
-                t.d.kind = RTG_TEX_PERLIN;
-            }
-            sc.textures.push_back(std::move(t));
-        }
+        sc.textures.push_back(std::move(t));
     }
+    return RTG_OK;
+}
 
-    // ParseTransformations (Parser.h:607-682)
-    if (const rtgh::XmlElement* tr = root->child("Transformations")) {
-        for (const rtgh::XmlElement* t : tr->all("Translation")) { float v[3]; scan3(text_of(t), v); sc.translations.insert(sc.translations.end(), v, v + 3); }
-        for (const rtgh::XmlElement* t : tr->all("Scaling")) { float v[3]; scan3(text_of(t), v); sc.scalings.insert(sc.scalings.end(), v, v + 3); }
-        for (const rtgh::XmlElement* t : tr->all("Rotation")) {
-            float v[4] = {0, 0, 0, 0};
-            sscanf(text_of(t), "%f %f %f %f", &v[0], &v[1], &v[2], &v[3]);
-            sc.rotations.insert(sc.rotations.end(), v, v + 4);
-        }
-        for (const rtgh::XmlElement* t : tr->all("Composite")) {
-            float v[16] = {0};
-            const char* p = text_of(t);
-            for (int k = 0; k < 16; k++) {                                  // XML row-major -> [col][row]
-                char* e;
-                float x = strtof(p, &e);
-                if (e == p) break;
-                v[k] = x;
-                p = e;
-            }
-            float cm[16];
-            for (int k = 0; k < 16; k++) cm[(k % 4) * 4 + k / 4] = v[k];
-            sc.composites.insert(sc.composites.end(), cm, cm + 16);
-        }
+// ParseTransformations (Parser.h:607-682)
+void parse_transformations(const Xml* root, rtgh_scene& sc) {
+    const Xml* tr = root->child("Transformations");
+    if (!tr) return;
+    for (const Xml* t : tr->all("Translation")) { float v[3]; scan3(text_of(t), v); sc.translations.insert(sc.translations.end(), v, v + 3); }
+    for (const Xml* t : tr->all("Scaling")) { float v[3]; scan3(text_of(t), v); sc.scalings.insert(sc.scalings.end(), v, v + 3); }
+    for (const Xml* t : tr->all("Rotation")) {
+        float v[4] = {0, 0, 0, 0};
+        sscanf(text_of(t), "%f %f %f %f", &v[0], &v[1], &v[2], &v[3]);
+        sc.rotations.insert(sc.rotations.end(), v, v + 4);
     }
-
-    // ParseVertices / ParseTextureCoordinates (Parser.h:684-767): atof -> double -> float
-    {
-        std::vector<double> v = numbers(child_text(root.get(), "VertexData"));
-        for (size_t k = 0; k + 2 < v.size(); k += 3)
-            sc.vertices.insert(sc.vertices.end(), {(float)v[k], (float)v[k + 1], (float)v[k + 2]});
-        std::vector<double> t = numbers(child_text(root.get(), "TexCoordData"));
-        for (size_t k = 0; k + 1 < t.size(); k += 2) sc.texcoords.insert(sc.texcoords.end(), {(float)t[k], (float)t[k + 1]});
-    }
-
-    // ParseObjects (Parser.h:798-1195); hw7: <LightSphere> after the spheres, <LightMesh> after the meshes
-    const rtgh::XmlElement* oe = root->child("Objects");
-    if (!oe) return fail(RTG_ERR_INVALID, "no <Objects>");
-    auto common = [&](const rtgh::XmlElement* el, ObjData& o) {
-        o.d.center = 1; o.d.radius = 1.0f; o.d.v[0] = 1; o.d.v[1] = 2; o.d.v[2] = 3;   // rtg/scene.py defaults
-        attr_int(el, "id", o.d.id);
-        o.d.material = 1;
-        query_int(child_text(el, "Material"), o.d.material);
-        if (const char* x = child_text(el, "Transformations")) parse_object_transformations(x, o.xf);
-        if (const char* x = child_text(el, "Textures")) {
-            std::vector<int> t = parse_textures_list(x);
-            o.d.num_textures = (int)t.size();
-            for (size_t k = 0; k < t.size(); k++) o.d.textures[k] = t[k];
+    for (const Xml* t : tr->all("Composite")) {
+        float v[16] = {0};
+        const char* p = text_of(t);
+        for (int k = 0; k < 16; k++) {                                  // XML row-major -> [col][row]
+            char* e;
+            float x = strtof(p, &e);
+            if (e == p) break;
+            v[k] = x;
+            p = e;
         }
-        if (el->child("MotionBlur")) scan3(child_text(el, "MotionBlur"), o.d.blur);
-    };
-    auto light = [&](const rtgh::XmlElement* el, ObjData& o) {
+        float cm[16];
+        for (int k = 0; k < 16; k++) cm[(k % 4) * 4 + k / 4] = v[k];
+        sc.composites.insert(sc.composites.end(), cm, cm + 16);
+    }
+}
+
+// ParseVertices / ParseTextureCoordinates (Parser.h:684-767): atof -> double -> float
+void parse_vertex_data(const Xml* root, rtgh_scene& sc) {
+    std::vector<double> v = numbers(child_text(root, "VertexData"));
+    for (size_t k = 0; k + 2 < v.size(); k += 3)
+        sc.vertices.insert(sc.vertices.end(), {(float)v[k], (float)v[k + 1], (float)v[k + 2]});
+    std::vector<double> t = numbers(child_text(root, "TexCoordData"));
+    for (size_t k = 0; k + 1 < t.size(); k += 2) sc.texcoords.insert(sc.texcoords.end(), {(float)t[k], (float)t[k + 1]});
+}
+
+// what every object element holds (ParseObjects, Parser.h:798-1195)
+void parse_object_common(const Xml* el, ObjData& o) {
+    o.d.center = 1; o.d.radius = 1.0f; o.d.v[0] = 1; o.d.v[1] = 2; o.d.v[2] = 3;   // rtg/scene.py defaults
+    attr_int(el, "id", o.d.id);
+    o.d.material = 1;
+    query_int(child_text(el, "Material"), o.d.material);
+    if (const char* x = child_text(el, "Transformations")) parse_object_transformations(x, o.xf);
+    if (const char* x = child_text(el, "Textures")) {
+        std::vector<int> t = parse_textures_list(x);
+        o.d.num_textures = (int)t.size();
+        for (size_t k = 0; k < t.size(); k++) o.d.textures[k] = t[k];
+    }
+    if (el->child("MotionBlur")) scan3(child_text(el, "MotionBlur"), o.d.blur);
+    if (el->name == "LightSphere" || el->name == "LightMesh") {                     // hw7: the object emits
         o.d.is_light = 1;
         scan3(child_text(el, "Radiance"), o.d.radiance);
-    };
-    for (const char* tag : {"Sphere", "LightSphere"})
-        for (const rtgh::XmlElement* el : oe->all(tag)) {
-            ObjData o;
-            o.d.type = RTG_OBJ_SPHERE;
-            common(el, o);
-            o.d.center = 1; o.d.radius = 1.0f;
-            query_int(child_text(el, "Center"), o.d.center);
-            query_float(child_text(el, "Radius"), o.d.radius);
-            if (strcmp(tag, "LightSphere") == 0) light(el, o);
-            sc.objects.push_back(std::move(o));
-        }
-    for (const rtgh::XmlElement* el : oe->all("Triangle")) {
-        ObjData o;
-        o.d.type = RTG_OBJ_TRIANGLE;
-        common(el, o);
-        if (const char* s = child_text(el, "Indices")) sscanf(s, "%d %d %d", &o.d.v[0], &o.d.v[1], &o.d.v[2]);
-        sc.objects.push_back(std::move(o));
     }
-    const int mesh_start = (int)sc.objects.size();
-    std::vector<const rtgh::XmlElement*> meshes = oe->all("Mesh");
-    for (const rtgh::XmlElement* el : oe->all("LightMesh")) meshes.push_back(el);
-    for (const rtgh::XmlElement* el : meshes) {
+}
+
+int parse_meshes(const Xml* oe, const std::string& base, rtgh_scene& sc) {
+    std::vector<const Xml*> meshes = oe->all("Mesh");
+    for (const Xml* el : oe->all("LightMesh")) meshes.push_back(el);
+    for (const Xml* el : meshes) {
         ObjData o;
         o.d.type = RTG_OBJ_MESH;
-        common(el, o);
-        if (el->name == "LightMesh") light(el, o);
+        parse_object_common(el, o);
         o.d.smooth = attr_prefix(el, "shadingMode", "smooth");
-        const rtgh::XmlElement* fe = el->child("Faces");
+        const Xml* fe = el->child("Faces");
         if (!fe) return fail(RTG_ERR_INVALID, "mesh without <Faces>");
         const std::string* ply = nullptr;
         for (const auto& a : fe->attrs)
             if (strncmp(a.first.c_str(), "plyFile", 7) == 0) { ply = &a.second; break; }
-        if (ply) {                                                          // Parser.h:1020-1106
+        if (ply) {      // Parser.h:1020-1106: the file's vertices and texture coordinates are appended to the scene's
             Ply P;
             int rc = read_ply(base + *ply, P);
             if (rc) return rc;
@@ -758,15 +741,14 @@ int parse(const std::string& xml_path, rtgh_scene& sc) {
             const int vertex_count = (int)(sc.vertices.size() / 3) + 1;
             o.faces.reserve(6 * P.fcount.size());
             size_t q = 0;
-            for (int cnt : P.fcount) {
+            for (int cnt : P.fcount) {                                      // quads split (0,1,2),(2,3,0)
                 const int64_t* f = P.fidx.data() + q;
                 q += (size_t)cnt;
-                if (cnt == 4) {
-                    o.faces.insert(o.faces.end(), {(int)(f[0] + vertex_count), (int)(f[1] + vertex_count), (int)(f[2] + vertex_count)});
-                    o.faces.insert(o.faces.end(), {(int)(f[2] + vertex_count), (int)(f[3] + vertex_count), (int)(f[0] + vertex_count)});
-                } else if (cnt >= 3) {
-                    o.faces.insert(o.faces.end(), {(int)(f[0] + vertex_count), (int)(f[1] + vertex_count), (int)(f[2] + vertex_count)});
-                }
+                auto tri = [&](int a, int b, int c) {
+                    o.faces.insert(o.faces.end(), {(int)(f[a] + vertex_count), (int)(f[b] + vertex_count), (int)(f[c] + vertex_count)});
+                };
+                if (cnt >= 3) tri(0, 1, 2);
+                if (cnt == 4) tri(2, 3, 0);
             }
             for (double x : P.xyz) sc.vertices.push_back((float)x);
             o.d.texture_offset = texture_offset - vertex_count;
@@ -781,15 +763,18 @@ int parse(const std::string& xml_path, rtgh_scene& sc) {
         }
         sc.objects.push_back(std::move(o));
     }
-    for (const rtgh::XmlElement* el : oe->all("MeshInstance")) {           // Parser.h:1151-1195
+    return RTG_OK;
+}
+
+// <MeshInstance> (Parser.h:1151-1195): the base is looked up among the meshes, objects[mesh_start..)
+int parse_mesh_instances(const Xml* oe, int mesh_start, rtgh_scene& sc) {
+    for (const Xml* el : oe->all("MeshInstance")) {
         InstData it;
         attr_int(el, "id", it.d.id);
         int base_id = 0;
         attr_int(el, "baseMeshId", base_id);
         if (const std::string* rt = el->attr("resetTransform")) {
-            std::string v = lower(*rt);
-            size_t a = v.find_first_not_of(" \t\r\n"), b = v.find_last_not_of(" \t\r\n");
-            v = a == std::string::npos ? "" : v.substr(a, b - a + 1);
+            const std::string v = trim(lower(*rt));
             it.d.reset_transform = v == "true" || v == "1";
         }
         it.d.material = 1;
@@ -803,63 +788,117 @@ int parse(const std::string& xml_path, rtgh_scene& sc) {
         it.d.base_object = found;
         sc.instances.push_back(it);
     }
+    return RTG_OK;
+}
 
-    // ParseLights (Parser.h:1197-1315): Point, Directional, Spot, Area, SphericalDirectional
-    if (const rtgh::XmlElement* le = root->child("Lights")) {
-        scan3(child_text(le, "AmbientLight"), sc.ambient);
-        for (const rtgh::XmlElement* l : le->all("PointLight")) {
-            rtg_light_desc d{};
-            d.type = RTG_LIGHT_POINT; d.texture = -1; d.direction[1] = -1;
-            scan3(child_text(l, "Position"), d.position);
-            scan3(child_text(l, "Intensity"), d.intensity);
-            sc.lights.push_back(d);
+// ParseObjects (Parser.h:798-1195); hw7: <LightSphere> after the spheres, <LightMesh> after the meshes
+int parse_objects(const Xml* root, const std::string& base, rtgh_scene& sc) {
+    const Xml* oe = root->child("Objects");
+    if (!oe) return fail(RTG_ERR_INVALID, "no <Objects>");
+    for (const char* tag : {"Sphere", "LightSphere"})
+        for (const Xml* el : oe->all(tag)) {
+            ObjData o;
+            o.d.type = RTG_OBJ_SPHERE;
+            parse_object_common(el, o);
+            query_int(child_text(el, "Center"), o.d.center);
+            query_float(child_text(el, "Radius"), o.d.radius);
+            sc.objects.push_back(std::move(o));
         }
-        for (const rtgh::XmlElement* l : le->all("DirectionalLight")) {
-            rtg_light_desc d{};
-            d.type = RTG_LIGHT_DIRECTIONAL; d.texture = -1;
-            scan3(child_text(l, "Direction"), d.direction);
-            scan3(child_text(l, "Radiance"), d.intensity);
-            sc.lights.push_back(d);
-        }
-        for (const rtgh::XmlElement* l : le->all("SpotLight")) {
-            rtg_light_desc d{};
-            d.type = RTG_LIGHT_SPOT; d.texture = -1;
-            scan3(child_text(l, "Position"), d.position);
-            scan3(child_text(l, "Direction"), d.direction);
-            scan3(child_text(l, "Intensity"), d.intensity);
-            query_float(child_text(l, "CoverageAngle"), d.coverage_deg);
-            query_float(child_text(l, "FalloffAngle"), d.falloff_deg);
-            sc.lights.push_back(d);
-        }
-        for (const rtgh::XmlElement* l : le->all("AreaLight")) {
-            rtg_light_desc d{};
-            d.type = RTG_LIGHT_AREA; d.texture = -1;
-            scan3(child_text(l, "Position"), d.position);
-            scan3(child_text(l, "Normal"), d.direction);
-            scan3(child_text(l, l->child("Radiance") ? "Radiance" : "Intensity"), d.intensity);
-            query_float(child_text(l, "Size"), d.size);
-            sc.lights.push_back(d);
-        }
-        for (const rtgh::XmlElement* l : le->all("SphericalDirectionalLight")) {
-            sc.environment_light = (int)sc.lights.size();
-            int iid = 1;
-            query_int(child_text(l, "ImageId"), iid);
-            if (iid < 1 || iid > (int)sc.images.size()) return fail(RTG_ERR_INVALID, "SphericalDirectionalLight ImageId out of range");
-            TexData t;
-            t.d.kind = RTG_TEX_IMAGE; t.d.decal = RTG_DECAL_NONE; t.d.interp = RTG_INTERP_BILINEAR; t.d.normalizer = 1;
-            t.d.bump_factor = 1.0f; t.d.noise_conv = RTG_NC_LINEAR; t.d.noise_scale = 1.0f;
-            t.image_id = iid;
-            int rc = image(sc.images[iid - 1], t);
-            if (rc) return rc;
-            sc.textures.push_back(std::move(t));
-            rtg_light_desc d{};
-            d.type = RTG_LIGHT_ENVIRONMENT; d.texture = (int)sc.textures.size() - 1; d.direction[1] = -1;
-            sc.lights.push_back(d);
-        }
+    for (const Xml* el : oe->all("Triangle")) {
+        ObjData o;
+        o.d.type = RTG_OBJ_TRIANGLE;
+        parse_object_common(el, o);
+        if (const char* s = child_text(el, "Indices")) sscanf(s, "%d %d %d", &o.d.v[0], &o.d.v[1], &o.d.v[2]);
+        sc.objects.push_back(std::move(o));
     }
-    // Scene ctor: the last replace_background texture (src/Scene.cpp:494-500)
+    const int mesh_start = (int)sc.objects.size();
+    int rc = parse_meshes(oe, base, sc);
+    if (rc) return rc;
+    return parse_mesh_instances(oe, mesh_start, sc);
+}
+
+// ParseLights (Parser.h:1197-1315): Point, Directional, Spot, Area, SphericalDirectional
+int parse_lights(const Xml* root, ImageCache& cache, rtgh_scene& sc) {
+    const Xml* le = root->child("Lights");
+    if (!le) return RTG_OK;
+    scan3(child_text(le, "AmbientLight"), sc.ambient);
+    auto new_light = [](int type) { rtg_light_desc d{}; d.type = type; d.texture = -1; return d; };
+    for (const Xml* l : le->all("PointLight")) {
+        rtg_light_desc d = new_light(RTG_LIGHT_POINT);
+        d.direction[1] = -1;
+        scan3(child_text(l, "Position"), d.position);
+        scan3(child_text(l, "Intensity"), d.intensity);
+        sc.lights.push_back(d);
+    }
+    for (const Xml* l : le->all("DirectionalLight")) {
+        rtg_light_desc d = new_light(RTG_LIGHT_DIRECTIONAL);
+        scan3(child_text(l, "Direction"), d.direction);
+        scan3(child_text(l, "Radiance"), d.intensity);
+        sc.lights.push_back(d);
+    }
+    for (const Xml* l : le->all("SpotLight")) {
+        rtg_light_desc d = new_light(RTG_LIGHT_SPOT);
+        scan3(child_text(l, "Position"), d.position);
+        scan3(child_text(l, "Direction"), d.direction);
+        scan3(child_text(l, "Intensity"), d.intensity);
+        query_float(child_text(l, "CoverageAngle"), d.coverage_deg);
+        query_float(child_text(l, "FalloffAngle"), d.falloff_deg);
+        sc.lights.push_back(d);
+    }
+    for (const Xml* l : le->all("AreaLight")) {
+        rtg_light_desc d = new_light(RTG_LIGHT_AREA);
+        scan3(child_text(l, "Position"), d.position);
+        scan3(child_text(l, "Normal"), d.direction);
+        scan3(child_text(l, l->child("Radiance") ? "Radiance" : "Intensity"), d.intensity);
+        query_float(child_text(l, "Size"), d.size);
+        sc.lights.push_back(d);
+    }
+    for (const Xml* l : le->all("SphericalDirectionalLight")) {
+        sc.environment_light = (int)sc.lights.size();
+        int iid = 1;
+        query_int(child_text(l, "ImageId"), iid);
+        if (iid < 1 || iid > (int)sc.images.size()) return fail(RTG_ERR_INVALID, "SphericalDirectionalLight ImageId out of range");
+        TexData t;
+        t.d.kind = RTG_TEX_IMAGE; t.d.decal = RTG_DECAL_NONE; t.d.interp = RTG_INTERP_BILINEAR; t.d.normalizer = 1;
+        t.d.bump_factor = 1.0f; t.d.noise_conv = RTG_NC_LINEAR; t.d.noise_scale = 1.0f;
+        t.image_id = iid;
+        int rc = image_texels(cache, sc.images[iid - 1], t);
+        if (rc) return rc;
+        sc.textures.push_back(std::move(t));
+        rtg_light_desc d = new_light(RTG_LIGHT_ENVIRONMENT);
+        d.texture = (int)sc.textures.size() - 1; d.direction[1] = -1;
+        sc.lights.push_back(d);
+    }
+    return RTG_OK;
+}
+
+// Scene ctor: the last replace_background texture (src/Scene.cpp:494-500)
+void find_background_texture(rtgh_scene& sc) {
     for (size_t i = 0; i < sc.textures.size(); i++)
         if (sc.textures[i].d.decal == RTG_DECAL_REPLACE_BACKGROUND) sc.background_texture = (int)i;
+}
+
+int parse(const std::string& xml_path, rtgh_scene& sc) {
+    std::string src;
+    if (!read_file(xml_path, src)) return fail(RTG_ERR_INVALID, "cannot read " + xml_path);
+    std::string err;
+    rtgh::XmlParser xp;
+    auto parsed = xp.parse(src, err);
+    if (!parsed) return fail(RTG_ERR_INVALID, err);
+    const Xml* root = parsed.get();
+    const size_t slash = xml_path.rfind('/');
+    const std::string base = slash == std::string::npos ? "" : xml_path.substr(0, slash + 1);
+    ImageCache cache;
+    int rc;
+    parse_scene_attributes(root, sc);
+    parse_cameras(root, sc);
+    parse_materials(root, parse_brdfs(root), sc);
+    if ((rc = parse_textures(root, base, cache, sc))) return rc;
+    parse_transformations(root, sc);
+    parse_vertex_data(root, sc);
+    if ((rc = parse_objects(root, base, sc))) return rc;
+    if ((rc = parse_lights(root, cache, sc))) return rc;
+    find_background_texture(sc);
     return RTG_OK;
 }
 
@@ -1087,11 +1126,6 @@ int32_t rtgh_save_image(const char* name, const float* rgb, int32_t nx, int32_t 
     });
 }
 
-// Scene::renderScene (src/Scene.cpp:294-363): precompute once, render and save every camera.
-int32_t rtgh_render_scene(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
-    return rtgh_render_scene_multi(xml_path, device, 0, seed, out_dir);
-}
-
 // Where a camera's image goes: its <ImageName>, or that file name under out_dir.
 static std::string output_name(const CamData& c, const char* out_dir) {
     std::string name = c.image_name;
@@ -1122,158 +1156,6 @@ static int save_camera_images(const CamData& c, const std::string& name, const s
     return rc;
 }
 
-int32_t rtgh_render_scene_multi(const char* xml_path, int32_t device, int32_t num_devices, uint64_t seed,
-                                const char* out_dir) {
-    return guarded([&]() -> int32_t {
-        if (num_devices < 0 || num_devices > 64) return fail(RTG_ERR_INVALID, "num_devices");
-        // num_devices >= 1: the multi-GPU path (rtg_render_opts.devices = device, device+1, ...),
-        // even for one GPU (one RCCL rank); 0: the single-device render
-        const int visible = rtg_device_count();
-        if (num_devices > visible) return fail(RTG_ERR_NO_DEVICE, "more devices requested than visible");
-        std::vector<int32_t> devs(num_devices);
-        for (int r = 0; r < num_devices; r++) devs[r] = (device + r) % std::max(visible, 1);
-        rtgh_scene* sc = nullptr;
-        int rc = rtgh_parse_xml(xml_path, &sc);
-        if (rc) return rc;
-        rtg_scene* gpu = nullptr;
-        rtg_build_opts bo{};
-        bo.bvh_builder = RTG_BVH_AUTO;   // tlas / traversal_tree: automatic (0)
-        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
-        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
-        printf("BVH construction complete.\n");
-        for (const CamData& c : sc->cameras) {
-            std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
-            rtg_render_opts o{};
-            o.seed = seed;
-            o.num_devices = num_devices;   // row-block shards, one host thread per GPU, RCCL gather
-            o.devices = num_devices > 0 ? devs.data() : nullptr;
-            rc = rtg_render(gpu, &c.d, &o, rgb.data());
-            if (rc) { g_err = rtg_last_error(); break; }
-            const std::string name = output_name(c, out_dir);
-            rc = save_camera_images(c, name, rgb, device);
-            if (rc) break;
-            rtg_render_stats st{};
-            rtg_last_render_stats(gpu, &st);
-            printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s\n", name.c_str(), st.render_ms, st.total_rays / (st.render_ms * 1e3),
-                   st.devices, st.devices == 1 ? "" : "s");
-        }
-        rtg_scene_destroy(gpu);
-        rtgh_free(sc);
-        return rc;
-    });
-}
-
-// The same camera loop on progressive frames (rtg_frame): rounds of `step` samples, the files rewritten
-// and an error line printed after each, a camera stopped early once its mean standard error is small
-// enough against its mean luminance.
-int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
-                                      int32_t step, double target_error) {
-    return guarded([&]() -> int32_t {
-        if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
-        if (!(target_error >= 0.0)) return fail(RTG_ERR_INVALID, "target error must not be negative");
-        const double kFltMin = 1.17549435082228750797e-38;     // FLT_MIN
-        rtgh_scene* sc = nullptr;
-        int rc = rtgh_parse_xml(xml_path, &sc);
-        if (rc) return rc;
-        rtg_scene* gpu = nullptr;
-        rtg_build_opts bo{};
-        bo.bvh_builder = RTG_BVH_AUTO;
-        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
-        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
-        printf("BVH construction complete.\n");
-        for (const CamData& c : sc->cameras) {
-            std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
-            rtg_render_opts o{};
-            o.seed = seed;
-            rtg_frame_opts fo{};
-            fo.moments = 1;
-            rtg_frame* fr = nullptr;
-            rc = rtg_frame_create(gpu, &c.d, &o, &fo, &fr);
-            if (rc) { g_err = rtg_last_error(); break; }
-            const std::string name = output_name(c, out_dir);
-            const int total = c.d.num_samples;
-            for (int done = 0; done < total && rc == RTG_OK;) {
-                const int n = step < total - done ? step : total - done;
-                rtg_frame_error er{};
-                if ((rc = rtg_frame_add_samples(fr, n, nullptr)) || (rc = rtg_frame_resolve(fr, rgb.data())) ||
-                    (rc = rtg_frame_error_stats(fr, &er))) {
-                    g_err = rtg_last_error();
-                    break;
-                }
-                done += n;
-                if ((rc = save_camera_images(c, name, rgb, device))) break;
-                printf("%s: %d/%d spp, mean_sem %.6g, mean_luminance %.6g\n", name.c_str(), done, total, er.mean_sem,
-                       er.mean_luminance);
-                fflush(stdout);
-                // (one sample has no variance yet: its standard error reads 0, which is no reason to stop)
-                if (target_error > 0.0 && done >= 2 && er.mean_sem <= target_error * (er.mean_luminance > kFltMin ? er.mean_luminance : kFltMin)) break;
-            }
-            rtg_frame_destroy(fr);
-            if (rc) break;
-        }
-        rtg_scene_destroy(gpu);
-        rtgh_free(sc);
-        return rc;
-    });
-}
-
-// The progressive loop with adaptive sampling: frames in sample order 1 with moments, rounds
-// of `step` positions; after each round the pixels whose standard error is at most rel_tol x their mean
-// luminance (and that hold at least min_samples) are retired and traced no further.  A camera ends with
-// its last active pixel or its last sample.
-int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
-                                   int32_t step, double rel_tol, int32_t min_samples) {
-    return guarded([&]() -> int32_t {
-        if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
-        if (!(rel_tol >= 0.0) || !(rel_tol <= 3.0e38)) return fail(RTG_ERR_INVALID, "adaptive tolerance must be finite and not negative");
-        rtgh_scene* sc = nullptr;
-        int rc = rtgh_parse_xml(xml_path, &sc);
-        if (rc) return rc;
-        rtg_scene* gpu = nullptr;
-        rtg_build_opts bo{};
-        bo.bvh_builder = RTG_BVH_AUTO;
-        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
-        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
-        printf("BVH construction complete.\n");
-        for (const CamData& c : sc->cameras) {
-            std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
-            rtg_render_opts o{};
-            o.seed = seed;
-            rtg_frame_opts fo{};
-            fo.moments = 1;
-            fo.order = 1;
-            rtg_frame* fr = nullptr;
-            rc = rtg_frame_create(gpu, &c.d, &o, &fo, &fr);
-            if (rc) { g_err = rtg_last_error(); break; }
-            const std::string name = output_name(c, out_dir);
-            const int total = c.d.num_samples;
-            rtg_frame_adapt ad{};
-            ad.rel_tol = (float)rel_tol;
-            ad.min_samples = min_samples;
-            int32_t active = rtg_frame_active_pixels(fr);
-            for (int done = 0; done < total && active > 0 && rc == RTG_OK;) {
-                const int n = step < total - done ? step : total - done;
-                rtg_frame_error er{};
-                if ((rc = rtg_frame_add_samples(fr, n, nullptr)) || (rc = rtg_frame_retire(fr, &ad, &active)) ||
-                    (rc = rtg_frame_resolve(fr, rgb.data())) || (rc = rtg_frame_error_stats(fr, &er))) {
-                    g_err = rtg_last_error();
-                    break;
-                }
-                done += n;
-                if ((rc = save_camera_images(c, name, rgb, device))) break;
-                printf("%s: %d/%d spp, mean_sem %.6g, mean_luminance %.6g, active %d\n", name.c_str(), done, total,
-                       er.mean_sem, er.mean_luminance, (int)active);
-                fflush(stdout);
-            }
-            rtg_frame_destroy(fr);
-            if (rc) break;
-        }
-        rtg_scene_destroy(gpu);
-        rtgh_free(sc);
-        return rc;
-    });
-}
-
 // A feature image's name: `suffix` before the extension of the camera's image name (a dot that starts the
 // file name is no extension).
 static std::string aov_name(const std::string& name, const char* suffix) {
@@ -1283,118 +1165,224 @@ static std::string aov_name(const std::string& name, const char* suffix) {
     return dot == std::string::npos ? name + suffix : name.substr(0, dot) + suffix + name.substr(dot);
 }
 
-// rtgh_render_scene's camera loop with the first-hit feature images (rtg_render_aov).
-int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
-    return guarded([&]() -> int32_t {
-        rtgh_scene* sc = nullptr;
-        int rc = rtgh_parse_xml(xml_path, &sc);
-        if (rc) return rc;
-        rtg_scene* gpu = nullptr;
-        rtg_build_opts bo{};
-        bo.bvh_builder = RTG_BVH_AUTO;
-        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
-        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
-        printf("BVH construction complete.\n");
-        for (const CamData& c : sc->cameras) {
-            const size_t np = (size_t)c.d.nx * c.d.ny;
-            std::vector<float> rgb(np * 3), normal(np * 3), albedo(np * 3), depth(np), img(np * 3);
-            rtg_render_opts o{};
-            o.seed = seed;
-            rc = rtg_render(gpu, &c.d, &o, rgb.data());
-            if (rc) { g_err = rtg_last_error(); break; }
-            const std::string name = output_name(c, out_dir);
-            if ((rc = save_camera_images(c, name, rgb, device))) break;
-            rtg_render_stats st{};
-            rtg_last_render_stats(gpu, &st);
-            rtg_aov_buffers ab{};
-            ab.depth = depth.data(); ab.normal = normal.data(); ab.albedo = albedo.data();
-            rc = rtg_render_aov(gpu, &c.d, &o, nullptr, &ab);
-            if (rc) { g_err = rtg_last_error(); break; }
-            for (size_t i = 0; i < np * 3; i++) img[i] = (normal[i] * 0.5f + 0.5f) * 255.0f;
-            if ((rc = rtgh_save_image(aov_name(name, "_normal").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-            for (size_t i = 0; i < np * 3; i++) img[i] = albedo[i] * 255.0f;
-            if ((rc = rtgh_save_image(aov_name(name, "_albedo").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-            for (size_t i = 0; i < np * 3; i++) img[i] = depth[i / 3];
-            if ((rc = rtgh_save_image(aov_name(name, "_depth").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-            rtg_render_stats sa{};
-            rtg_last_render_stats(gpu, &sa);
-            printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s; feature buffers %.1f ms\n", name.c_str(), st.render_ms,
-                   st.total_rays / (st.render_ms * 1e3), st.devices, st.devices == 1 ? "" : "s", sa.render_ms);
-        }
-        rtg_scene_destroy(gpu);
-        rtgh_free(sc);
-        return rc;
-    });
+// The three first-hit feature images of a camera (rtg_render_aov); img is scratch of an image's size.
+static int save_feature_images(const CamData& c, const std::string& name, const float* normal, const float* albedo,
+                               const float* depth, std::vector<float>& img) {
+    int rc;
+    for (size_t i = 0; i < img.size(); i++) img[i] = (normal[i] * 0.5f + 0.5f) * 255.0f;
+    if ((rc = rtgh_save_image(aov_name(name, "_normal").c_str(), img.data(), c.d.nx, c.d.ny))) return rc;
+    for (size_t i = 0; i < img.size(); i++) img[i] = albedo[i] * 255.0f;
+    if ((rc = rtgh_save_image(aov_name(name, "_albedo").c_str(), img.data(), c.d.nx, c.d.ny))) return rc;
+    for (size_t i = 0; i < img.size(); i++) img[i] = depth[i / 3];
+    return rtgh_save_image(aov_name(name, "_depth").c_str(), img.data(), c.d.nx, c.d.ny);
 }
 
-// rtgh_render_scene's camera loop with a denoised image per camera (rtg_denoise): one frame with
-// moments per camera, all its samples added at once (rtg_render's bits), the first-hit guides of the full sample
-// range, albedo demodulation, and the variance of each pixel's mean luminance where there are two samples.
-static int32_t render_scene_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir, bool aov) {
-    return guarded([&]() -> int32_t {
-        rtgh_scene* sc = nullptr;
-        int rc = rtgh_parse_xml(xml_path, &sc);
-        if (rc) return rc;
-        rtg_scene* gpu = nullptr;
-        rtg_build_opts bo{};
-        bo.bvh_builder = RTG_BVH_AUTO;
-        rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
-        if (rc) { g_err = rtg_last_error(); rtgh_free(sc); return rc; }
-        printf("BVH construction complete.\n");
-        for (const CamData& c : sc->cameras) {
-            const size_t np = (size_t)c.d.nx * c.d.ny;
-            std::vector<float> rgb(np * 3), normal(np * 3), albedo(np * 3), depth(np), var(np), img(np * 3);
-            rtg_render_opts o{};
-            o.seed = seed;
-            rtg_frame_opts fo{};
-            fo.moments = 1;
-            rtg_frame* fr = nullptr;
-            rc = rtg_frame_create(gpu, &c.d, &o, &fo, &fr);
-            if (rc) { g_err = rtg_last_error(); break; }
-            const int total = c.d.num_samples;
-            rtg_render_stats st{};
-            if ((rc = rtg_frame_add_samples(fr, total, nullptr)) == RTG_OK) {
-                rtg_last_render_stats(gpu, &st);
-                if ((rc = rtg_frame_resolve(fr, rgb.data())) == RTG_OK && total >= 2)
-                    rc = rtg_frame_moments(fr, nullptr, var.data());
-            }
-            if (rc) g_err = rtg_last_error();
-            rtg_frame_destroy(fr);
-            if (rc) break;
-            const std::string name = output_name(c, out_dir);
-            if ((rc = save_camera_images(c, name, rgb, device))) break;
-            rtg_aov_buffers ab{};
-            ab.depth = depth.data(); ab.normal = normal.data(); ab.albedo = albedo.data();
-            rc = rtg_render_aov(gpu, &c.d, &o, nullptr, &ab);
-            if (rc) { g_err = rtg_last_error(); break; }
-            if (aov) {
-                for (size_t i = 0; i < np * 3; i++) img[i] = (normal[i] * 0.5f + 0.5f) * 255.0f;
-                if ((rc = rtgh_save_image(aov_name(name, "_normal").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-                for (size_t i = 0; i < np * 3; i++) img[i] = albedo[i] * 255.0f;
-                if ((rc = rtgh_save_image(aov_name(name, "_albedo").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-                for (size_t i = 0; i < np * 3; i++) img[i] = depth[i / 3];
-                if ((rc = rtgh_save_image(aov_name(name, "_depth").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-            }
+// Owners of what a render holds: released on every return path and by every exception.
+struct Release {
+    void operator()(rtgh_scene* s) const { rtgh_free(s); }
+    void operator()(rtg_scene* s) const { rtg_scene_destroy(s); }
+    void operator()(rtg_frame* f) const { rtg_frame_destroy(f); }
+};
+using FrameOwner = std::unique_ptr<rtg_frame, Release>;
+struct LoadedScene {                                 // members go in reverse: the GPU scene, then the parsed one
+    std::unique_ptr<rtgh_scene, Release> parsed;
+    std::unique_ptr<rtg_scene, Release> gpu;
+};
+
+// Parse the XML and build it on the GPU: what Scene::renderScene finds done when it starts.
+static int load_scene(const char* xml_path, int32_t device, LoadedScene& out) {
+    rtgh_scene* sc = nullptr;
+    int rc = rtgh_parse_xml(xml_path, &sc);
+    if (rc) return rc;
+    out.parsed.reset(sc);
+    rtg_scene* gpu = nullptr;
+    rtg_build_opts bo{};
+    bo.bvh_builder = RTG_BVH_AUTO;   // tlas / traversal_tree: automatic (0)
+    rc = rtg_scene_create_ex(&sc->desc, device, &bo, &gpu);
+    if (rc) { g_err = rtg_last_error(); return rc; }
+    out.gpu.reset(gpu);
+    printf("BVH construction complete.\n");
+    return RTG_OK;
+}
+
+// What the exported camera loops differ by.
+struct RenderMode {
+    int32_t num_devices = 0;     // >= 1: the multi-GPU path (rtg_render_opts.devices = device, device+1, ...: row-block
+                                 // shards, one host thread per GPU, RCCL gather), even for one GPU; 0: single-device
+    int32_t step = 0;            // >= 1: progressive, rounds of `step` samples on a frame (render_camera_rounds)
+    double target_error = 0.0;   // > 0: a camera stops once its mean standard error <= this x its mean luminance
+    double rel_tol = -1.0;       // >= 0: adaptive sampling: after each round the pixels whose standard
+    int32_t min_samples = 0;     // error <= rel_tol x their mean luminance and that hold min_samples are retired
+    bool aov = false;            // also the first-hit feature images
+    bool denoise = false;        // also the denoised image (rtg_denoise)
+};
+
+// A camera in rounds on a progressive frame: the files rewritten and an error line printed after each round.  It
+// stops early once its mean standard error is small enough against its mean luminance; the adaptive mode (sample
+// order 1) ends a camera with its last active pixel or its last sample.
+static int render_camera_rounds(rtg_scene* gpu, const CamData& c, const rtg_render_opts& o, const std::string& name,
+                                int32_t device, const RenderMode& m) {
+    const double kFltMin = 1.17549435082228750797e-38;     // FLT_MIN
+    const bool adaptive = m.rel_tol >= 0.0;
+    std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
+    rtg_frame_opts fo{};
+    fo.moments = 1;
+    fo.order = adaptive ? 1 : 0;
+    rtg_frame* created = nullptr;
+    int rc = rtg_frame_create(gpu, &c.d, &o, &fo, &created);
+    if (rc) { g_err = rtg_last_error(); return rc; }
+    const FrameOwner fr(created);
+    rtg_frame_adapt ad{};
+    ad.rel_tol = (float)m.rel_tol;
+    ad.min_samples = m.min_samples;
+    int32_t active = adaptive ? rtg_frame_active_pixels(fr.get()) : 1;
+    const int total = c.d.num_samples;
+    for (int done = 0; done < total && active > 0;) {
+        const int n = m.step < total - done ? m.step : total - done;
+        rtg_frame_error er{};
+        if ((rc = rtg_frame_add_samples(fr.get(), n, nullptr)) || (adaptive && (rc = rtg_frame_retire(fr.get(), &ad, &active))) ||
+            (rc = rtg_frame_resolve(fr.get(), rgb.data())) || (rc = rtg_frame_error_stats(fr.get(), &er))) {
+            g_err = rtg_last_error();
+            return rc;
+        }
+        done += n;
+        if ((rc = save_camera_images(c, name, rgb, device))) return rc;
+        printf("%s: %d/%d spp, mean_sem %.6g, mean_luminance %.6g", name.c_str(), done, total, er.mean_sem, er.mean_luminance);
+        if (adaptive) printf(", active %d", (int)active);
+        printf("\n");
+        fflush(stdout);
+        // (one sample has no variance yet: its standard error reads 0, which is no reason to stop)
+        if (!adaptive && m.target_error > 0.0 && done >= 2 &&
+            er.mean_sem <= m.target_error * (er.mean_luminance > kFltMin ? er.mean_luminance : kFltMin)) break;
+    }
+    return RTG_OK;
+}
+
+// A camera in one go.  For the denoiser the samples go through a frame with moments, all added at once (rtg_render's
+// bits); the filter is guided by the feature buffers of the full sample range, with albedo demodulation and the
+// variance of each pixel's mean luminance where there are two samples.
+static int render_camera(rtg_scene* gpu, const CamData& c, const rtg_render_opts& o, const std::string& name,
+                         int32_t device, const RenderMode& m) {
+    const size_t np = (size_t)c.d.nx * c.d.ny;
+    const int total = c.d.num_samples;
+    std::vector<float> rgb(np * 3), var(m.denoise ? np : 0);
+    rtg_render_stats st{}, sa{};             // of the render (read before rtg_render_aov replaces them), of the features
+    int rc;
+    if (m.denoise) {
+        rtg_frame_opts fo{};
+        fo.moments = 1;
+        rtg_frame* created = nullptr;
+        rc = rtg_frame_create(gpu, &c.d, &o, &fo, &created);
+        if (rc) { g_err = rtg_last_error(); return rc; }
+        const FrameOwner fr(created);
+        if ((rc = rtg_frame_add_samples(fr.get(), total, nullptr)) == RTG_OK) {
+            rtg_last_render_stats(gpu, &st);
+            if ((rc = rtg_frame_resolve(fr.get(), rgb.data())) == RTG_OK && total >= 2)
+                rc = rtg_frame_moments(fr.get(), nullptr, var.data());
+        }
+    } else if ((rc = rtg_render(gpu, &c.d, &o, rgb.data())) == RTG_OK) {
+        rtg_last_render_stats(gpu, &st);
+    }
+    if (rc) { g_err = rtg_last_error(); return rc; }
+    if ((rc = save_camera_images(c, name, rgb, device))) return rc;
+    if (m.aov || m.denoise) {
+        std::vector<float> normal(np * 3), albedo(np * 3), depth(np), img(np * 3);
+        rtg_aov_buffers ab{};
+        ab.depth = depth.data(); ab.normal = normal.data(); ab.albedo = albedo.data();
+        rc = rtg_render_aov(gpu, &c.d, &o, nullptr, &ab);
+        if (rc) { g_err = rtg_last_error(); return rc; }
+        rtg_last_render_stats(gpu, &sa);
+        if (m.aov && (rc = save_feature_images(c, name, normal.data(), albedo.data(), depth.data(), img))) return rc;
+        if (m.denoise) {
             for (size_t i = 0; i < np; i++) var[i] = var[i] / (float)total;     // of the pixel's mean
             rtg_denoise_inputs di{rgb.data(), normal.data(), depth.data(), albedo.data(), total >= 2 ? var.data() : nullptr};
             rc = rtg_denoise(device, &di, c.d.nx, c.d.ny, nullptr, img.data());
-            if (rc) { g_err = rtg_last_error(); break; }
-            if ((rc = rtgh_save_image(aov_name(name, "_denoised").c_str(), img.data(), c.d.nx, c.d.ny))) break;
-            printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s; denoised\n", name.c_str(), st.render_ms,
-                   st.total_rays / (st.render_ms * 1e3), st.devices, st.devices == 1 ? "" : "s");
+            if (rc) { g_err = rtg_last_error(); return rc; }
+            if ((rc = rtgh_save_image(aov_name(name, "_denoised").c_str(), img.data(), c.d.nx, c.d.ny))) return rc;
         }
-        rtg_scene_destroy(gpu);
-        rtgh_free(sc);
-        return rc;
+    }
+    printf("%s: %.1f ms, %.1f Mray/s, %d GPU%s", name.c_str(), st.render_ms, st.total_rays / (st.render_ms * 1e3), st.devices,
+           st.devices == 1 ? "" : "s");
+    if (m.denoise) printf("; denoised");
+    else if (m.aov) printf("; feature buffers %.1f ms", sa.render_ms);
+    printf("\n");
+    return RTG_OK;
+}
+
+// Scene::renderScene (src/Scene.cpp:294-363): precompute once, render and save every camera.  The one camera
+// loop behind every rtgh_render_scene*; each of them checks its arguments before it comes here.
+static int32_t render_cameras(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir, const RenderMode& m) {
+    return guarded([&]() -> int32_t {
+        std::vector<int32_t> devs(m.num_devices);
+        const int visible = m.num_devices > 0 ? rtg_device_count() : 0;
+        for (int r = 0; r < m.num_devices; r++) devs[r] = (device + r) % std::max(visible, 1);
+        LoadedScene sc;
+        int rc = load_scene(xml_path, device, sc);
+        if (rc) return rc;
+        for (const CamData& c : sc.parsed->cameras) {
+            rtg_render_opts o{};
+            o.seed = seed;
+            o.num_devices = m.num_devices;
+            o.devices = m.num_devices > 0 ? devs.data() : nullptr;
+            const std::string name = output_name(c, out_dir);
+            rc = m.step >= 1 ? render_camera_rounds(sc.gpu.get(), c, o, name, device, m)
+                             : render_camera(sc.gpu.get(), c, o, name, device, m);
+            if (rc) return rc;
+        }
+        return RTG_OK;
     });
 }
 
+int32_t rtgh_render_scene(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
+    return rtgh_render_scene_multi(xml_path, device, 0, seed, out_dir);
+}
+
+int32_t rtgh_render_scene_multi(const char* xml_path, int32_t device, int32_t num_devices, uint64_t seed,
+                                const char* out_dir) {
+    if (num_devices < 0 || num_devices > 64) return fail(RTG_ERR_INVALID, "num_devices");
+    if (num_devices > rtg_device_count()) return fail(RTG_ERR_NO_DEVICE, "more devices requested than visible");
+    RenderMode m;
+    m.num_devices = num_devices;
+    return render_cameras(xml_path, device, seed, out_dir, m);
+}
+
+int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                      int32_t step, double target_error) {
+    if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
+    if (!(target_error >= 0.0)) return fail(RTG_ERR_INVALID, "target error must not be negative");
+    RenderMode m;
+    m.step = step;
+    m.target_error = target_error;
+    return render_cameras(xml_path, device, seed, out_dir, m);
+}
+
+int32_t rtgh_render_scene_adaptive(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                   int32_t step, double rel_tol, int32_t min_samples) {
+    if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
+    if (!(rel_tol >= 0.0) || !(rel_tol <= 3.0e38)) return fail(RTG_ERR_INVALID, "adaptive tolerance must be finite and not negative");
+    RenderMode m;
+    m.step = step;
+    m.rel_tol = rel_tol;
+    m.min_samples = min_samples;
+    return render_cameras(xml_path, device, seed, out_dir, m);
+}
+
+int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
+    RenderMode m;
+    m.aov = true;
+    return render_cameras(xml_path, device, seed, out_dir, m);
+}
+
 int32_t rtgh_render_scene_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
-    return render_scene_denoise(xml_path, device, seed, out_dir, false);
+    RenderMode m;
+    m.denoise = true;
+    return render_cameras(xml_path, device, seed, out_dir, m);
 }
 
 int32_t rtgh_render_scene_denoise_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir) {
-    return render_scene_denoise(xml_path, device, seed, out_dir, true);
+    RenderMode m;
+    m.aov = m.denoise = true;
+    return render_cameras(xml_path, device, seed, out_dir, m);
 }
 
 }  // extern "C"

@@ -85,3 +85,58 @@ def test_cli_envmap_exr_texture(gpu, tmp_path):
         img = r.render(0)
     ref, _, _, _ = pyoracle.Oracle(sc).render(0)
     assert float(np.nanmax(np.abs(img.astype(np.float64) - ref))) < 1e-3
+
+
+def _two_camera_scene():
+    """cornell with two cameras of different shapes (a buffer sized for the wrong camera would show):
+    16 x 12 to a.png, 12 x 16 with a <Tonemap> to b.exr (and b.png), 8 samples each."""
+    import copy
+    sc = scenegen.cornell(16, 12, spp=8)
+    first = sc.cameras[0]
+    first.image_name = "a.png"
+    second = copy.deepcopy(first)
+    second.id, second.nx, second.ny = 2, 12, 16
+    second.image_name, second.tonemap = "b.exr", (0.18, 1.0, 1.0, 2.2)
+    sc.cameras.append(second)
+    return sc
+
+
+def _run_cli(xml, cwd, gpu, options):
+    """rtg_cli in `cwd` (image names are relative to it): its files' bytes, and its stdout lines with the
+    measured numbers masked."""
+    import re
+    cwd.mkdir()
+    r = subprocess.run([native.CLI_PATH, xml, "--device", str(gpu), *options], cwd=cwd, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr
+    lines = [re.sub(r"\S+ (ms|Mray/s)", r"# \1", ln) for ln in r.stdout.splitlines()]
+    return {p.name: p.read_bytes() for p in cwd.iterdir()}, lines
+
+
+@pytest.mark.parametrize("options", [
+    [], ["--devices", "1"], ["--progressive", "4"],
+    ["--progressive", "4", "--adaptive", "0.1", "--min-samples", "4"], ["--aov"], ["--denoise", "--aov"],
+], ids=lambda o: " ".join(o) or "plain")
+def test_cli_cameras_are_independent(gpu, tmp_path, options):
+    """A scene with two cameras, in every mode of the command line: each camera's files and stdout lines are those
+    of a scene that holds that camera alone (nothing carries over from one camera into the next), and the scene
+    is built once."""
+    sc = _two_camera_scene()
+    both = write_xml(sc, str(tmp_path / "both.xml"))
+    files, lines = _run_cli(both, tmp_path / "both", gpu, options)
+    bvh = "BVH construction complete."
+    assert lines.count(bvh) == 1 and lines[0] == bvh
+    alone_files, alone_lines = {}, [bvh]
+    for k in range(len(sc.cameras)):
+        one = _two_camera_scene()
+        one.cameras = one.cameras[k:k + 1]
+        f, ln = _run_cli(write_xml(one, str(tmp_path / f"cam{k}.xml")), tmp_path / f"cam{k}", gpu, options)
+        assert ln[0] == bvh and len(ln) > 1
+        assert not set(f) & set(alone_files)
+        alone_files.update(f)
+        alone_lines += ln[1:]
+    assert {"a.png", "b.exr", "b.png"} <= set(files)
+    assert sorted(files) == sorted(alone_files)
+    for name in sorted(files):
+        assert files[name] == alone_files[name], name
+    assert lines == alone_lines
