@@ -686,6 +686,54 @@ int32_t rtg_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t nx, in
 int32_t rtg_denoise_device(int32_t device, const rtg_denoise_inputs* in_device, int32_t nx, int32_t ny,
                            const rtg_denoise_opts* opts, float* rgb_out_device, void* stream);
 
+/* ---- ABI 10 additions: denoising a frame on the device ------------------------
+   Additive: the version stays 10, no struct grows.
+
+   rtg_frame_denoise filters the frame's current image without anything leaving the device: the image is
+   rtg_frame_resolve's; normal, depth and albedo are rtg_render_aov's over the camera's whole sample range
+   (first 0, count 0) under the frame's seed and traversal, tile_band 0 as rtg_render_aov sets it; the
+   albedo is used only when demodulate != 0.  For a frame with moments and samples_done >= 2 the variance
+   of each pixel's mean luminance opens the luminance stop: with n the pixel's own count (samples_done for
+   an active pixel, the kept count for a retired one), (M2 / (float)(n - 1)) / (float)n for n >= 2 -- two
+   correctly rounded float32 divides, rtg_frame_moments' variance over the float32 count -- and +0 for
+   n < 2.  A frame without moments, or with one sample, runs without the luminance stop.  The result is,
+   bit for bit, rtg_denoise over those arrays.  A frame window with first_sample > 0 and an order-1 frame
+   are allowed (the guides still cover the camera's whole range).
+
+   Checked before any device work, in this order: NULL frame or output (RTG_ERR_INVALID); a frame whose
+   state a failed call lost, or without samples (RTG_ERR_INVALID); the options, by rtg_denoise's rules;
+   a sharded frame (row_stride > 1) or a compact_rows frame (RTG_ERR_UNSUPPORTED).
+
+   State.  The first of these calls on a frame allocates, and rtg_frame_destroy releases: the guide cache
+   (normal, depth, albedo in image order, 28 B per pixel), traced once by that call and never again --
+   the guides are a function of scene, camera, seed and traversal, all fixed at rtg_frame_create, so
+   rtg_frame_set_state, rtg_frame_set_retired and further samples leave them valid; the call inputs
+   (resolved rgb and variance, 16 B per pixel), rewritten by every call; the filter's workspace (56 B per
+   pixel), kept between calls.  In all 100 B per pixel, about 207 MB at 1920x1080.  A frame that never
+   denoises allocates nothing and launches what it did before.
+
+   The call that traces the guides leaves rtg_last_render_stats as rtg_render_aov does (primary_rays =
+   total_rays = pixels x num_samples); a later call leaves the scene's stats untouched.  Calls may
+   interleave with renders, other frames and rtg_render_aov on the scene, never run concurrently with
+   them; they change no bit of the accumulator, the moments or the counts.  The work is enqueued behind
+   `stream` (hipStream_t); synchronous on return.  rgb_out_device must not alias the frame's own buffers
+   (no call hands those out). */
+typedef struct rtg_frame_guides {   /* 40 bytes; DEVICE pointers on the scene's device, each may be NULL, not all */
+    float* rgb;       /* 3 per pixel: what rtg_frame_resolve_device writes */
+    float* normal;    /* 3 per pixel */
+    float* depth;     /* 1 per pixel */
+    float* albedo;    /* 3 per pixel */
+    float* variance;  /* 1 per pixel: variance of the pixel's MEAN luminance */
+} rtg_frame_guides;
+/* opts may be NULL (defaults); rgb_out: host, ny * nx * 3 floats. */
+int32_t rtg_frame_denoise(rtg_frame* frame, const rtg_denoise_opts* opts, int32_t demodulate, float* rgb_out);
+int32_t rtg_frame_denoise_device(rtg_frame* frame, const rtg_denoise_opts* opts, int32_t demodulate,
+                                 float* rgb_out_device, void* stream);
+/* Copies the five arrays the filter would read at the frame's current state into the caller's device
+   arrays (refusals as above, without the options).  variance where the frame has none (no moments, or
+   fewer than two samples): RTG_ERR_INVALID. */
+int32_t rtg_frame_guides_device(rtg_frame* frame, const rtg_frame_guides* out_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,14 @@ extern int32_t rtgh_render_scene_aov(const char* xml_path, int32_t device, uint6
 extern int32_t rtgh_render_scene_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir);
 /* The same, and rtgh_render_scene_aov's three feature images from the same guides. */
 extern int32_t rtgh_render_scene_denoise_aov(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir);
+/* rtgh_render_scene_progressive, and after every round the round's frame filtered on the device
+   (rtg_frame_denoise with albedo demodulation, DESIGN.md §21: the guides are traced by the first round and kept,
+   the variance is the frame's own) and written through rtgh_save_image, named like the camera's image with
+   _denoised before the extension.  The per-round lines and the camera's own image files are those of
+   rtgh_render_scene_progressive; run to num_samples, the last _denoised file is byte-identical to
+   rtgh_render_scene_denoise's.  (`extern` as above.) */
+extern int32_t rtgh_render_scene_progressive_denoise(const char* xml_path, int32_t device, uint64_t seed,
+                                                     const char* out_dir, int32_t step, double target_error);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
 //                  <d, 0>: a (32 + 4d) x (8 + 4d) tile of both records staged in LDS (d = 1, 2);
 //                  <0, 0>: every tap two 16-byte global loads (any stride)
 //   k_dn_finish    remodulation; invalid pixels copy their input through
+//   k_frame_inputs a frame's sums, counts and M2 -> the resolved rgb and the variance of the mean (§21)
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -244,6 +245,33 @@ k_dn_finish(const float* __restrict__ rgb, const float* __restrict__ albedo, con
     out[3 * i + 2] = b;
 }
 
+// rtg_frame_denoise's per-call inputs, one lane per pixel of a whole, uncompacted frame (its
+// owned-row order is image order): rgb as k_finalize / k_finalize_counts resolve it -- the sum over the pixel's
+// own count, divided only when that exceeds 1, 0 without samples -- and, with kVar, the variance of the mean
+// luminance (M2 / (float)(n - 1)) / (float)n, +0 for n < 2.  The 12-byte sums travel as three dwords in one
+// access (they are 4-byte aligned), mean / M2 as one 8-byte load.
+struct DnRgb { float r, g, b; };
+template <bool kAdapt, bool kVar>
+__global__ void __launch_bounds__(256)
+k_frame_inputs(const DnRgb* __restrict__ acc, const unsigned* __restrict__ cnt, const float2* __restrict__ mom, int npix,
+               int done, DnRgb* __restrict__ rgb, float* __restrict__ variance) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    int n = done;
+    if (kAdapt) {
+        const unsigned c = cnt[i];
+        if (c & kRetiredBit) n = (int)(c & ~kRetiredBit);
+    }
+    DnRgb s = acc[i];
+    if (n < 1) s = DnRgb{0.0f, 0.0f, 0.0f};
+    if (n > 1) {
+        const float fn = (float)n;
+        s.r = s.r / fn; s.g = s.g / fn; s.b = s.b / fn;
+    }
+    rgb[i] = s;
+    if (kVar) variance[i] = n >= 2 ? (mom[i].y / (float)(n - 1)) / (float)n : 0.0f;
+}
+
 template <class T>
 struct DnBuf {
     T* p = nullptr;
@@ -274,18 +302,30 @@ void dn_launch(bool var, dim3 grid, dim3 block, hipStream_t st, const float4* G,
 // Strides up to this run the LDS-tiled pass (measured on the MI355X: DESIGN.md §18, profiles/denoise.json).
 constexpr int kDnLdsMaxStride = 2;
 
+// the 56 B per pixel of workspace, one block (a hipMalloc costs more than a pass): G, S, S', slopes
+size_t denoise_workspace_bytes(int nx, int ny) {
+    const size_t n = (size_t)nx * ny;
+    return sizeof(float4) * (3 * n + (n + 1) / 2);
+}
+
 int denoise_device(const rtg_denoise_inputs& in, int nx, int ny, const rtg_denoise_opts& o, float* out, hipStream_t st,
                    std::string& err) {
-    const size_t n = (size_t)nx * ny;
-    // the 56 B per pixel of workspace in one allocation (a hipMalloc costs more than a pass): G, S, S', slopes
-    DnBuf<float4> ws;
-    hipError_t e;
-    if ((e = ws.alloc(3 * n + (n + 1) / 2)) != hipSuccess) {
+    DnBuf<char> ws;
+    const hipError_t e = ws.alloc(denoise_workspace_bytes(nx, ny));
+    if (e != hipSuccess) {
         err = std::string("denoise hipMalloc: ") + hipGetErrorString(e);
         return -1;
     }
-    float4 *G = ws.p, *a = ws.p + n, *b = ws.p + 2 * n;
-    float2* slope = (float2*)(ws.p + 3 * n);
+    return denoise_device_ws(in, nx, ny, o, out, ws.p, st, err);
+}
+
+int denoise_device_ws(const rtg_denoise_inputs& in, int nx, int ny, const rtg_denoise_opts& o, float* out, void* workspace,
+                      hipStream_t st, std::string& err) {
+    const size_t n = (size_t)nx * ny;
+    hipError_t e;
+    float4* const ws = static_cast<float4*>(workspace);
+    float4 *G = ws, *a = ws + n, *b = ws + 2 * n;
+    float2* slope = (float2*)(ws + 3 * n);
     int lds_max = kDnLdsMaxStride;
     if (const char* s = getenv("RTG_DENOISE_LDS")) lds_max = atoi(s);      // dev knob: 0 = every pass direct
     DnEvents ev;
@@ -321,6 +361,29 @@ int denoise_device(const rtg_denoise_inputs& in, int nx, int ny, const rtg_denoi
         fprintf(stderr, "\n");
     }
     return 0;
+}
+
+void launch_frame_inputs(const float* acc, const unsigned* cnt, const float* mom, int npix, int done, float* rgb,
+                         float* variance, hipStream_t st) {
+    if (npix <= 0) return;
+    const dim3 grid((unsigned)((npix + 255) / 256)), block(256);
+    const DnRgb* a = reinterpret_cast<const DnRgb*>(acc);
+    const float2* m = reinterpret_cast<const float2*>(mom);
+    DnRgb* o = reinterpret_cast<DnRgb*>(rgb);
+    DnEvents ev;
+    ev.on = getenv("RTG_DENOISE_TIMING") != nullptr;
+    ev.mark(st);
+    if (cnt && variance) hipLaunchKernelGGL((k_frame_inputs<true, true>), grid, block, 0, st, a, cnt, m, npix, done, o, variance);
+    else if (cnt) hipLaunchKernelGGL((k_frame_inputs<true, false>), grid, block, 0, st, a, cnt, m, npix, done, o, variance);
+    else if (variance) hipLaunchKernelGGL((k_frame_inputs<false, true>), grid, block, 0, st, a, cnt, m, npix, done, o, variance);
+    else hipLaunchKernelGGL((k_frame_inputs<false, false>), grid, block, 0, st, a, cnt, m, npix, done, o, variance);
+    ev.mark(st);
+    if (ev.on && ev.n == 2 && hipEventSynchronize(ev.e[1]) == hipSuccess) {     // (the dev knob alone waits here)
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ev.e[0], ev.e[1]);
+        fprintf(stderr, "[rtg] frame inputs %d pixels (adaptive %d, variance %d) ms: %.4f\n", npix, cnt != nullptr,
+                variance != nullptr, ms);
+    }
 }
 
 }  // namespace rtg

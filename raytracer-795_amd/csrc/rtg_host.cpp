@@ -3481,6 +3481,11 @@ struct rtg_frame {
     DBuf cnt;                                // per owned pixel: kRetiredBit | samples kept, 0 while active
     DBuf active;                             // the active pixels' tile-order indices, ascending
     DBuf scan;                               // per-block counts of the list build + the total; mask staging
+    // Denoising on the device; nothing below is allocated before the first rtg_frame_denoise.
+    bool guides_ready = false;               // dn_guides holds the camera's first-hit guides (traced once)
+    DBuf dn_guides;                          // image order: normal 3, albedo 3, depth 1 floats per pixel (planes)
+    DBuf dn_in;                              // the call's inputs: resolved rgb 3, variance 1 floats per pixel (planes)
+    DBuf dn_ws;                              // the filter's workspace (denoise_workspace_bytes), kept between calls
 };
 
 // The multiplier of sample order 1 (include/rtg.h): 1 for n <= 2, else the smallest m >= max(1, round
@@ -3603,6 +3608,7 @@ int32_t rtg_frame_destroy(rtg_frame* f) {
     if (f->scene->device >= 0) (void)hipSetDevice(f->scene->device);
     f->acc.release(); f->mom.release(); f->err.release();
     f->cnt.release(); f->active.release(); f->scan.release();
+    f->dn_guides.release(); f->dn_in.release(); f->dn_ws.release();
     {
         std::lock_guard<std::mutex> lk(g_frames_mu);
         const auto it = std::find(g_frame_scenes.begin(), g_frame_scenes.end(), f->scene);
@@ -3934,10 +3940,8 @@ int32_t rtg_tonemap(int32_t device, const float* hdr, int32_t nx, int32_t ny, co
 }
 
 // rtg_denoise's arguments, checked before the device is touched; *eff receives the options with defaults resolved.
-static int check_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t nx, int32_t ny, const rtg_denoise_opts* opts,
-                         const float* out, rtg_denoise_opts* eff) {
-    if (!in || !in->rgb || !in->normal || !in->depth || !out) return fail(RTG_ERR_INVALID, "null argument");
-    if (nx < 1 || ny < 1 || (long long)nx * ny > (1LL << 30)) return fail(RTG_ERR_INVALID, "denoise image size");
+// The options' own rules stand alone for rtg_frame_denoise.
+static int check_denoise_opts(const rtg_denoise_opts* opts, rtg_denoise_opts* eff) {
     rtg_denoise_opts o{};
     if (opts) o = *opts;
     if (o.iterations < 0 || o.iterations > 8) return fail(RTG_ERR_INVALID, "denoise iterations must be 0 (default) or 1..8");
@@ -3952,6 +3956,15 @@ static int check_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t n
     if (o.sigma_z == 0.0f) o.sigma_z = 1.0f;
     if (o.normal_power_log2 == 0) o.normal_power_log2 = 6;
     *eff = o;
+    return RTG_OK;
+}
+
+static int check_denoise(int32_t device, const rtg_denoise_inputs* in, int32_t nx, int32_t ny, const rtg_denoise_opts* opts,
+                         const float* out, rtg_denoise_opts* eff) {
+    if (!in || !in->rgb || !in->normal || !in->depth || !out) return fail(RTG_ERR_INVALID, "null argument");
+    if (nx < 1 || ny < 1 || (long long)nx * ny > (1LL << 30)) return fail(RTG_ERR_INVALID, "denoise image size");
+    const int rc = check_denoise_opts(opts, eff);
+    if (rc) return rc;
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return fail(RTG_ERR_NO_DEVICE, "no such device");
     return RTG_OK;
@@ -4105,77 +4118,104 @@ static int aov_window(const rtg_camera_desc* cam, int first, int count, int& win
     return RTG_OK;
 }
 
+}  // extern "C"
+
+// rtg_render_aov's device buffers and events, released on every return path.
+struct AovScratch {
+    DBuf rec, tile, img;
+    hipEvent_t e[2] = {};
+    ~AovScratch() { rec.release(); tile.release(); img.release(); for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// rtg_render_aov up to its downloads: the placed planes stay on the device, in w.img (ip: nout pixels of the
+// image layout); *stats receives the stats the call reports.  Synchronous on return.  rtg_frame_denoise keeps
+// three of the planes as its guide cache.
+static int aov_device(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, const rtg_aov_opts* aopts,
+                      AovScratch& w, AovPlanes& ip, size_t& nout, rtg_render_stats* stats) {
+    rtg_aov_opts ao{};
+    if (aopts) ao = *aopts;
+    if (ao.pad[0] || ao.pad[1]) return fail(RTG_ERR_INVALID, "rtg_aov_opts.pad must be 0");
+    int window = 0, rc;
+    if ((rc = aov_window(cam, ao.first_sample, ao.sample_count, window))) return rc;
+    rtg_render_opts o{};
+    if (opts) o = *opts;
+    if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_UNSUPPORTED, "feature buffers render on the scene's device only");
+    o.tile_band = 0;                    // the renders' pixel order with the default band height
+    PassDevA ps{};
+    if ((rc = pixel_order(o, cam, ps))) return rc;
+    ps.s0 = ao.first_sample; ps.ns = window;
+    if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+    HIP_TRY(hipSetDevice(s->device));
+    const int rows_owned = ps.rows_owned, npix = rows_owned * cam->nx;
+    const int out_rows = o.compact_rows ? rows_owned : cam->ny;
+    nout = (size_t)out_rows * cam->nx;
+    const CameraDev cd = make_camera(cam);
+
+    // 11 words per pixel: hits 1, depth 1, normal 3, albedo 3, ids 3
+    if ((rc = w.tile.grow(44 * std::max<size_t>(npix, 1))) || (rc = w.img.grow(44 * std::max<size_t>(nout, 1)))) return rc;
+    auto planes = [](void* base, size_t n) {
+        int* p = static_cast<int*>(base);
+        return AovPlanes{p, reinterpret_cast<float*>(p + n), reinterpret_cast<float*>(p + 2 * n),
+                         reinterpret_cast<float*>(p + 5 * n), p + 8 * n, n};
+    };
+    const AovPlanes tp = planes(w.tile.p, (size_t)npix);
+    ip = planes(w.img.p, nout);
+    // passes: pixel ranges of whole tiles with at most 4M sample slots (128 MB of records) -- a longer
+    // window takes one pixel per pass (its slots stay within int: make_camera's sample grid ends at 10^6
+    // samples) -- dealt round-robin to up to four of the scene's lanes, each with its own records, so one
+    // pass's reduction (few, long lanes) runs beside the next passes' traversal; the passes write
+    // disjoint pixel ranges of the planes, and the null stream joins the lanes before the placement
+    const long long kSlots = 4LL << 20;
+    const int chunk = window >= kSlots ? 1 : (int)std::max<long long>(1, kSlots / window >= 64 ? (kSlots / window) & ~63LL : kSlots / window);
+    if ((long long)window * chunk > (1LL << 31) - 1) return fail(RTG_ERR_UNSUPPORTED, "sample window too long");
+    const int npasses = (npix + chunk - 1) / chunk;
+    const int L = std::max(1, std::min(4, npasses));
+    if ((rc = ensure_lanes(s, L))) return rc;
+    const size_t slots = (size_t)std::min(chunk, std::max(npix, 1)) * window;
+    if ((rc = w.rec.grow(kAovRecBytes * slots * L))) return rc;
+    for (hipEvent_t& x : w.e) HIP_TRY(hipEventCreate(&x));
+    HIP_TRY(hipEventRecord(w.e[0], nullptr));
+    for (int k = 0; k < L; k++) HIP_TRY(hipStreamWaitEvent(s->lanes[k].st, w.e[0], 0));
+    int launches = 0;
+    for (int p0 = 0; p0 < npix; p0 += chunk, launches++) {
+        const int k = launches % L;
+        float4* rec_a = w.rec.as<float4>() + (size_t)2 * slots * k;
+        ps.p0 = p0; ps.npass = std::min(chunk, npix - p0);
+        launch_aov(s->sv, cd, ps, o.seed, o.traversal == 1, s->d_origprim.as<int>(), rec_a, rec_a + slots, tp, s->lanes[k].st);
+    }
+    for (int k = 0; k < L; k++) {
+        HIP_TRY(hipEventRecord(s->lanes[k].ev_join, s->lanes[k].st));
+        HIP_TRY(hipStreamWaitEvent(nullptr, s->lanes[k].ev_join, 0));
+    }
+    launch_aov_place(tp, ip, cam->nx, out_rows, ps, o.compact_rows != 0, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(w.e[1], nullptr));
+    HIP_TRY(hipEventSynchronize(w.e[1]));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, w.e[0], w.e[1]));
+    rtg_render_stats st{};
+    st.primary_rays = st.total_rays = (uint64_t)npix * (uint64_t)window;
+    st.render_ms = ms;
+    st.passes = launches;
+    st.devices = 1;
+    *stats = st;
+    return RTG_OK;
+}
+
+extern "C" {
+
 int32_t rtg_render_aov(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, const rtg_aov_opts* aopts,
                        const rtg_aov_buffers* out) {
     return guarded([&]() -> int32_t {
         if (!s || !cam || !out) return fail(RTG_ERR_INVALID, "null argument");
         if (!out->hits && !out->depth && !out->normal && !out->albedo && !out->ids)
             return fail(RTG_ERR_INVALID, "no output buffer");
-        rtg_aov_opts ao{};
-        if (aopts) ao = *aopts;
-        if (ao.pad[0] || ao.pad[1]) return fail(RTG_ERR_INVALID, "rtg_aov_opts.pad must be 0");
-        int window = 0, rc;
-        if ((rc = aov_window(cam, ao.first_sample, ao.sample_count, window))) return rc;
-        rtg_render_opts o{};
-        if (opts) o = *opts;
-        if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_UNSUPPORTED, "feature buffers render on the scene's device only");
-        o.tile_band = 0;                    // the renders' pixel order with the default band height
-        PassDevA ps{};
-        if ((rc = pixel_order(o, cam, ps))) return rc;
-        ps.s0 = ao.first_sample; ps.ns = window;
-        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
-        HIP_TRY(hipSetDevice(s->device));
-        const int rows_owned = ps.rows_owned, npix = rows_owned * cam->nx;
-        const int out_rows = o.compact_rows ? rows_owned : cam->ny;
-        const size_t nout = (size_t)out_rows * cam->nx;
-        const CameraDev cd = make_camera(cam);
-
-        struct Scratch {                    // RAII: released on every return path
-            DBuf rec, tile, img;
-            hipEvent_t e[2] = {};
-            ~Scratch() { rec.release(); tile.release(); img.release(); for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-        } w;
-        // 11 words per pixel: hits 1, depth 1, normal 3, albedo 3, ids 3
-        if ((rc = w.tile.grow(44 * std::max<size_t>(npix, 1))) || (rc = w.img.grow(44 * std::max<size_t>(nout, 1)))) return rc;
-        auto planes = [](void* base, size_t n) {
-            int* p = static_cast<int*>(base);
-            return AovPlanes{p, reinterpret_cast<float*>(p + n), reinterpret_cast<float*>(p + 2 * n),
-                             reinterpret_cast<float*>(p + 5 * n), p + 8 * n, n};
-        };
-        const AovPlanes tp = planes(w.tile.p, (size_t)npix), ip = planes(w.img.p, nout);
-        // passes: pixel ranges of whole tiles with at most 4M sample slots (128 MB of records) -- a longer
-        // window takes one pixel per pass (its slots stay within int: make_camera's sample grid ends at 10^6
-        // samples) -- dealt round-robin to up to four of the scene's lanes, each with its own records, so one
-        // pass's reduction (few, long lanes) runs beside the next passes' traversal; the passes write
-        // disjoint pixel ranges of the planes, and the null stream joins the lanes before the placement
-        const long long kSlots = 4LL << 20;
-        const int chunk = window >= kSlots ? 1 : (int)std::max<long long>(1, kSlots / window >= 64 ? (kSlots / window) & ~63LL : kSlots / window);
-        if ((long long)window * chunk > (1LL << 31) - 1) return fail(RTG_ERR_UNSUPPORTED, "sample window too long");
-        const int npasses = (npix + chunk - 1) / chunk;
-        const int L = std::max(1, std::min(4, npasses));
-        if ((rc = ensure_lanes(s, L))) return rc;
-        const size_t slots = (size_t)std::min(chunk, std::max(npix, 1)) * window;
-        if ((rc = w.rec.grow(kAovRecBytes * slots * L))) return rc;
-        for (hipEvent_t& x : w.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(w.e[0], nullptr));
-        for (int k = 0; k < L; k++) HIP_TRY(hipStreamWaitEvent(s->lanes[k].st, w.e[0], 0));
-        int launches = 0;
-        for (int p0 = 0; p0 < npix; p0 += chunk, launches++) {
-            const int k = launches % L;
-            float4* rec_a = w.rec.as<float4>() + (size_t)2 * slots * k;
-            ps.p0 = p0; ps.npass = std::min(chunk, npix - p0);
-            launch_aov(s->sv, cd, ps, o.seed, o.traversal == 1, s->d_origprim.as<int>(), rec_a, rec_a + slots, tp, s->lanes[k].st);
-        }
-        for (int k = 0; k < L; k++) {
-            HIP_TRY(hipEventRecord(s->lanes[k].ev_join, s->lanes[k].st));
-            HIP_TRY(hipStreamWaitEvent(nullptr, s->lanes[k].ev_join, 0));
-        }
-        launch_aov_place(tp, ip, cam->nx, out_rows, ps, o.compact_rows != 0, nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(w.e[1], nullptr));
-        HIP_TRY(hipEventSynchronize(w.e[1]));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, w.e[0], w.e[1]));
+        AovScratch w;
+        AovPlanes ip{};
+        size_t nout = 0;
+        rtg_render_stats st{};
+        const int rc = aov_device(s, cam, opts, aopts, w, ip, nout, &st);
+        if (rc) return rc;
         if (nout) {
             if (out->hits) HIP_TRY(hipMemcpy(out->hits, ip.hits, 4 * nout, hipMemcpyDeviceToHost));
             if (out->depth) HIP_TRY(hipMemcpy(out->depth, ip.depth, 4 * nout, hipMemcpyDeviceToHost));
@@ -4183,11 +4223,6 @@ int32_t rtg_render_aov(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
             if (out->albedo) HIP_TRY(hipMemcpy(out->albedo, ip.albedo, 12 * nout, hipMemcpyDeviceToHost));
             if (out->ids) HIP_TRY(hipMemcpy(out->ids, ip.ids, 12 * nout, hipMemcpyDeviceToHost));
         }
-        rtg_render_stats st{};
-        st.primary_rays = st.total_rays = (uint64_t)npix * (uint64_t)window;
-        st.render_ms = ms;
-        st.passes = launches;
-        st.devices = 1;
         s->stats = st;
         return RTG_OK;
     });
@@ -4220,6 +4255,138 @@ int32_t rtg_camera_rays(rtg_scene* s, const rtg_camera_desc* cam, uint64_t seed,
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(rays_out + (size_t)p0 * window, w.d.p, sizeof(rtg_ray) * n, hipMemcpyDeviceToHost));
         }
+        return RTG_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- denoising a frame on the device
+// The frame's denoise buffers are sized once and exactly (DBuf::grow keeps a margin for buffers that grow).
+static int frame_dn_alloc(DBuf& b, size_t bytes) {
+    if (b.p) return RTG_OK;
+    if (hipMalloc(&b.p, std::max<size_t>(bytes, 16)) != hipSuccess) {
+        b.p = nullptr;
+        return fail(RTG_ERR_OOM, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
+    }
+    b.bytes = bytes;
+    return RTG_OK;
+}
+
+static int frame_dn_whole(const rtg_frame* f) {
+    if (f->opts.row_stride > 1 || f->opts.compact_rows)
+        return fail(RTG_ERR_UNSUPPORTED, "denoising needs a whole frame: not sharded, not compact");
+    return RTG_OK;
+}
+
+static bool frame_dn_has_variance(const rtg_frame* f) { return f->moments && f->done >= 2; }
+
+struct FrameDnArrays { float *rgb, *normal, *depth, *albedo, *variance; };   // variance NULL where the frame has none
+
+// Fills the guide cache on its first use (need_guides), refreshes rgb and variance from the accumulator on `st`
+// (need_inputs) and names the five arrays.  Nothing is synchronised after the refresh.
+static int frame_dn_arrays(rtg_frame* f, bool need_guides, bool need_inputs, hipStream_t st, FrameDnArrays& a) {
+    const size_t n = (size_t)f->npix;
+    int rc;
+    HIP_TRY(hipSetDevice(f->scene->device));
+    if (need_guides && !f->guides_ready) {
+        if ((rc = frame_dn_alloc(f->dn_guides, sizeof(float) * 7 * n))) return rc;
+        // the tracer works on the scene's lanes behind the null stream: whatever `st` still holds comes first
+        HIP_TRY(hipStreamSynchronize(st));
+        rtg_render_opts o{};                 // what the guides depend on; aov_device sets tile_band = 0
+        o.seed = f->opts.seed;
+        o.traversal = f->opts.traversal;
+        AovScratch w;
+        AovPlanes ip{};
+        size_t nout = 0;
+        rtg_render_stats stats{};
+        if ((rc = aov_device(f->scene, &f->cam, &o, nullptr, w, ip, nout, &stats))) return rc;
+        if (nout != n) return fail(RTG_ERR_HIP, "guide planes of another size");
+        float* g = f->dn_guides.as<float>();
+        HIP_TRY(hipMemcpy(g, ip.normal, sizeof(float) * 3 * n, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(g + 3 * n, ip.albedo, sizeof(float) * 3 * n, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(g + 6 * n, ip.depth, sizeof(float) * n, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        f->scene->stats = stats;
+        f->guides_ready = true;
+    }
+    const bool var = frame_dn_has_variance(f);
+    if (need_inputs) {
+        if ((rc = frame_dn_alloc(f->dn_in, sizeof(float) * 4 * n))) return rc;
+        float* in = f->dn_in.as<float>();
+        launch_frame_inputs(f->acc.as<float>(), f->adaptive ? f->cnt.as<unsigned>() : nullptr, var ? f->mom.as<float>() : nullptr,
+                            f->npix, f->done, in, var ? in + 3 * n : nullptr, st);
+        HIP_TRY(hipGetLastError());
+    }
+    float* g = f->dn_guides.as<float>();
+    float* in = f->dn_in.as<float>();
+    a = FrameDnArrays{in, g, g ? g + 6 * n : nullptr, g ? g + 3 * n : nullptr, var && in ? in + 3 * n : nullptr};
+    return RTG_OK;
+}
+
+extern "C" {
+
+int32_t rtg_frame_denoise_device(rtg_frame* f, const rtg_denoise_opts* opts, int32_t demodulate, float* rgb_out_device,
+                                 void* stream) {
+    return guarded([&]() -> int32_t {
+        if (!f || !rgb_out_device) return fail(RTG_ERR_INVALID, "null argument");
+        int rc = frame_ready(f, false);
+        if (rc) return rc;
+        rtg_denoise_opts o{};
+        if ((rc = check_denoise_opts(opts, &o))) return rc;
+        if ((rc = frame_dn_whole(f))) return rc;
+        const hipStream_t st = (hipStream_t)stream;
+        FrameDnArrays a{};
+        if ((rc = frame_dn_arrays(f, true, true, st, a))) return rc;
+        if ((rc = frame_dn_alloc(f->dn_ws, denoise_workspace_bytes(f->cam.nx, f->cam.ny)))) return rc;
+        const rtg_denoise_inputs in{a.rgb, a.normal, a.depth, demodulate ? a.albedo : nullptr, a.variance};
+        std::string err;
+        if (denoise_device_ws(in, f->cam.nx, f->cam.ny, o, rgb_out_device, f->dn_ws.p, st, err)) return fail(RTG_ERR_HIP, err);
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_denoise(rtg_frame* f, const rtg_denoise_opts* opts, int32_t demodulate, float* rgb_out) {
+    return guarded([&]() -> int32_t {
+        if (!f || !rgb_out) return fail(RTG_ERR_INVALID, "null argument");
+        int rc = frame_ready(f, false);
+        if (rc) return rc;
+        rtg_denoise_opts o{};
+        if ((rc = check_denoise_opts(opts, &o))) return rc;
+        if ((rc = frame_dn_whole(f))) return rc;
+        HIP_TRY(hipSetDevice(f->scene->device));
+        const size_t bytes = sizeof(float) * 3 * (size_t)f->npix;
+        struct Dev { float* p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } d;
+        if (hipMalloc(&d.p, bytes) != hipSuccess) return fail(RTG_ERR_OOM, "denoise output buffer");
+        if ((rc = rtg_frame_denoise_device(f, opts, demodulate, d.p, nullptr))) return rc;
+        HIP_TRY(hipMemcpy(rgb_out, d.p, bytes, hipMemcpyDeviceToHost));
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_frame_guides_device(rtg_frame* f, const rtg_frame_guides* out, void* stream) {
+    return guarded([&]() -> int32_t {
+        if (!f || !out) return fail(RTG_ERR_INVALID, "null argument");
+        if (!out->rgb && !out->normal && !out->depth && !out->albedo && !out->variance)
+            return fail(RTG_ERR_INVALID, "no output buffer");
+        int rc = frame_ready(f, false);
+        if (rc) return rc;
+        if (out->variance && !frame_dn_has_variance(f))
+            return fail(RTG_ERR_INVALID, "frame has no variance: it needs moments and two samples");
+        if ((rc = frame_dn_whole(f))) return rc;
+        const hipStream_t st = (hipStream_t)stream;
+        const size_t n = (size_t)f->npix;
+        FrameDnArrays a{};
+        if ((rc = frame_dn_arrays(f, out->normal || out->depth || out->albedo, out->rgb || out->variance, st, a))) return rc;
+        const auto copy = [&](float* dst, const float* src, size_t floats) {
+            return dst ? hipMemcpyAsync(dst, src, sizeof(float) * floats, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        };
+        HIP_TRY(copy(out->rgb, a.rgb, 3 * n));
+        HIP_TRY(copy(out->normal, a.normal, 3 * n));
+        HIP_TRY(copy(out->depth, a.depth, n));
+        HIP_TRY(copy(out->albedo, a.albedo, 3 * n));
+        HIP_TRY(copy(out->variance, a.variance, n));
+        HIP_TRY(hipStreamSynchronize(st));
         return RTG_OK;
     });
 }

@@ -610,6 +610,16 @@ int tonemap_device(const float* hdr, int nx, int ny, const rtg_tonemap_desc& tm,
 // arrays, `o` holds the effective options (defaults resolved).
 int denoise_device(const rtg_denoise_inputs& in, int nx, int ny, const rtg_denoise_opts& o, float* out, hipStream_t st,
                    std::string& err);
+// The same over a workspace the caller keeps (denoise_workspace_bytes of device memory, 16-byte aligned);
+// denoise_device allocates one per call and runs this.
+size_t denoise_workspace_bytes(int nx, int ny);
+int denoise_device_ws(const rtg_denoise_inputs& in, int nx, int ny, const rtg_denoise_opts& o, float* out, void* workspace,
+                      hipStream_t st, std::string& err);
+// rtg_frame_denoise's per-call inputs from a whole, uncompacted frame: rgb[3 * i + c] as
+// launch_finalize / launch_finalize_counts resolve pixel i, variance[i] = (M2 / (float)(n - 1)) / (float)n for the
+// pixel's own count n >= 2, else +0.  cnt NULL: every pixel holds `done`; variance NULL: none written, mom unread.
+void launch_frame_inputs(const float* acc, const unsigned* cnt, const float* mom, int npix, int done, float* rgb,
+                         float* variance, hipStream_t st);
 
 // GPU BVH construction (rtg_bvh_gpu.hip): the reference median-split tree of one object.
 // nodes: breadth-first {left, right, start, end} (children -1: none); box: 6 floats per node

@@ -34,6 +34,13 @@
 // feature buffers and the per-pixel variance of a frame with moments, named with _denoised before the extension;
 // the image files themselves are the ones a run without it writes, byte for byte.  One GPU, in one go: not with
 // --progressive, --adaptive or --devices.
+//
+//   rtg_cli scene.xml --progressive K [--target-error E] --denoise-rounds ...
+//
+// --denoise-rounds (with --progressive) also rewrites the _denoised image after every round, filtered on the device
+// from the round's frame (rtg_frame_denoise: the guides are traced once, nothing is downloaded but the result); the
+// round lines and the camera's own files are those of --progressive alone.  Not with --adaptive, --devices, --aov
+// or --denoise.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,7 +53,7 @@ int main(int argc, char** argv) {
     int device = 0, devices = 0, progressive = 0;
     bool have_progressive = false, have_target = false;
     double target_error = 0.0, adaptive = 0.0;
-    bool have_adaptive = false, have_min = false, aov = false, denoise = false;
+    bool have_adaptive = false, have_min = false, aov = false, denoise = false, denoise_rounds = false;
     int min_samples = 2;
     unsigned long long seed = 0x5EED2026ull;
     for (int i = 1; i < argc; i++) {
@@ -60,12 +67,18 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--min-samples") && i + 1 < argc) { min_samples = atoi(argv[++i]); have_min = true; }
         else if (!strcmp(argv[i], "--aov")) aov = true;
         else if (!strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!strcmp(argv[i], "--denoise-rounds")) denoise_rounds = true;
         else if (argv[i][0] == '-') { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
         else xml = argv[i];
     }
     if (!xml) {
         fprintf(stderr, "usage: %s scene.xml [--device N] [--devices G] [--seed S] [--out-dir DIR] "
-                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]]] [--aov] [--denoise]\n", argv[0]);
+                        "[--progressive K [--target-error E | --adaptive REL [--min-samples M]] [--denoise-rounds]] [--aov] [--denoise]\n", argv[0]);
+        return 2;
+    }
+    if (denoise_rounds && (!have_progressive || have_adaptive || devices > 0 || aov || denoise)) {
+        fprintf(stderr, "rtg_cli: --denoise-rounds needs --progressive: it cannot be combined with --adaptive, --devices, "
+                        "--aov or --denoise\n");
         return 2;
     }
     if (have_progressive && devices > 0) {
@@ -91,6 +104,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     const int rc = have_adaptive ? rtgh_render_scene_adaptive(xml, device, seed, out_dir, progressive, adaptive, min_samples)
+                 : denoise_rounds   ? rtgh_render_scene_progressive_denoise(xml, device, seed, out_dir, progressive, target_error)
                  : have_progressive ? rtgh_render_scene_progressive(xml, device, seed, out_dir, progressive, target_error)
                  : denoise          ? (aov ? rtgh_render_scene_denoise_aov(xml, device, seed, out_dir)
                                            : rtgh_render_scene_denoise(xml, device, seed, out_dir))

@@ -1215,16 +1215,18 @@ struct RenderMode {
     int32_t min_samples = 0;     // error <= rel_tol x their mean luminance and that hold min_samples are retired
     bool aov = false;            // also the first-hit feature images
     bool denoise = false;        // also the denoised image (rtg_denoise)
+    bool denoise_rounds = false; // progressive: also the denoised image after every round (rtg_frame_denoise, §21)
 };
 
 // A camera in rounds on a progressive frame: the files rewritten and an error line printed after each round.  It
 // stops early once its mean standard error is small enough against its mean luminance; the adaptive mode (sample
-// order 1) ends a camera with its last active pixel or its last sample.
+// order 1) ends a camera with its last active pixel or its last sample.  With denoise_rounds the round's frame is
+// also filtered on the device (rtg_frame_denoise: guides traced once, by the first round) and <name>_denoised rewritten.
 static int render_camera_rounds(rtg_scene* gpu, const CamData& c, const rtg_render_opts& o, const std::string& name,
                                 int32_t device, const RenderMode& m) {
     const double kFltMin = 1.17549435082228750797e-38;     // FLT_MIN
     const bool adaptive = m.rel_tol >= 0.0;
-    std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3);
+    std::vector<float> rgb((size_t)c.d.nx * c.d.ny * 3), den(m.denoise_rounds ? rgb.size() : 0);
     rtg_frame_opts fo{};
     fo.moments = 1;
     fo.order = adaptive ? 1 : 0;
@@ -1247,6 +1249,10 @@ static int render_camera_rounds(rtg_scene* gpu, const CamData& c, const rtg_rend
         }
         done += n;
         if ((rc = save_camera_images(c, name, rgb, device))) return rc;
+        if (m.denoise_rounds) {
+            if ((rc = rtg_frame_denoise(fr.get(), nullptr, 1, den.data()))) { g_err = rtg_last_error(); return rc; }
+            if ((rc = rtgh_save_image(aov_name(name, "_denoised").c_str(), den.data(), c.d.nx, c.d.ny))) return rc;
+        }
         printf("%s: %d/%d spp, mean_sem %.6g, mean_luminance %.6g", name.c_str(), done, total, er.mean_sem, er.mean_luminance);
         if (adaptive) printf(", active %d", (int)active);
         printf("\n");
@@ -1353,6 +1359,17 @@ int32_t rtgh_render_scene_progressive(const char* xml_path, int32_t device, uint
     RenderMode m;
     m.step = step;
     m.target_error = target_error;
+    return render_cameras(xml_path, device, seed, out_dir, m);
+}
+
+int32_t rtgh_render_scene_progressive_denoise(const char* xml_path, int32_t device, uint64_t seed, const char* out_dir,
+                                              int32_t step, double target_error) {
+    if (step < 1) return fail(RTG_ERR_INVALID, "progressive step must be at least 1");
+    if (!(target_error >= 0.0)) return fail(RTG_ERR_INVALID, "target error must not be negative");
+    RenderMode m;
+    m.step = step;
+    m.target_error = target_error;
+    m.denoise_rounds = true;
     return render_cameras(xml_path, device, seed, out_dir, m);
 }
 

@@ -203,6 +203,12 @@ class DenoiseInputs(C.Structure):
     _fields_ = [("rgb", PF), ("normal", PF), ("depth", PF), ("albedo", PF), ("variance", PF)]
 
 
+class FrameGuides(C.Structure):
+    """rtg_frame_guides: device pointers, each may be 0, not all."""
+    _fields_ = [("rgb", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p),
+                ("variance", C.c_void_p)]
+
+
 class Hit(C.Structure):
     _fields_ = [("full", C.c_int32), ("object", C.c_int32), ("prim", C.c_int32), ("material", C.c_int32),
                 ("t", C.c_float), ("point", F3), ("normal", F3)]
@@ -266,6 +272,10 @@ EXPORTS = {
     "rtg_denoise": (C.c_int32, [C.c_int32, C.POINTER(DenoiseInputs), C.c_int32, C.c_int32, C.POINTER(DenoiseOpts), PF]),
     "rtg_denoise_device": (C.c_int32, [C.c_int32, C.POINTER(DenoiseInputs), C.c_int32, C.c_int32,
                                        C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]),
+    # ABI 10 additions: denoising a frame on the device
+    "rtg_frame_denoise": (C.c_int32, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_int32, PF]),
+    "rtg_frame_denoise_device": (C.c_int32, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_int32, C.c_void_p, C.c_void_p]),
+    "rtg_frame_guides_device": (C.c_int32, [C.c_void_p, C.POINTER(FrameGuides), C.c_void_p]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

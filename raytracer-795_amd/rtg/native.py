@@ -44,6 +44,9 @@ def load():
         lib.rtgh_render_scene_progressive.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32,
                                                       C.c_double]
         lib.rtgh_render_scene_progressive.restype = C.c_int32
+        lib.rtgh_render_scene_progressive_denoise.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32,
+                                                              C.c_double]
+        lib.rtgh_render_scene_progressive_denoise.restype = C.c_int32
         lib.rtgh_render_scene_adaptive.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_char_p, C.c_int32, C.c_double,
                                                    C.c_int32]
         lib.rtgh_render_scene_adaptive.restype = C.c_int32

@@ -566,11 +566,23 @@ def denoised_name(name: str) -> str:
     return aov_name(name, "_denoised")
 
 
-def _frame_denoise(self, demodulate: bool = True, **opts) -> np.ndarray:
+def _denoise_opts(iterations: int = 0, sigma_l: float = 0.0, sigma_z: float = 0.0, normal_power_log2: int = 0):
+    return A.DenoiseOpts(int(iterations), float(sigma_l), float(sigma_z), int(normal_power_log2))
+
+
+def _frame_denoise(self, demodulate: bool = True, resident: bool = False, **opts) -> np.ndarray:
     """The frame's resolve() filtered by rtg.denoise under the camera's first-hit guides (Renderer.aov over
     its whole sample range, the frame's seed and traversal).  With moments and at least two samples the
     luminance stop runs on moments()[1] / counts()[0], the variance of each pixel's mean (0 for a pixel with
-    fewer than two samples).  `opts`: denoise's options.  Whole, uncompacted frames only."""
+    fewer than two samples).  `opts`: denoise's options.  Whole, uncompacted frames only.
+    resident=True computes the same bits without leaving the device (rtg_frame_denoise): the
+    guides are traced by the frame's first such call and kept, the filter's workspace stays with the frame."""
+    if resident:
+        out = np.empty((self.camera.ny, self.camera.nx, 3), np.float32)
+        do = _denoise_opts(**opts)
+        A.check(self.lib.rtg_frame_denoise(self.handle, C.byref(do), int(bool(demodulate)), out.ctypes.data_as(A.PF)),
+                self.lib)
+        return out
     o = self.opts
     if o.compact_rows or o.row_stride > 1 or self.rows != self.camera.ny or o.num_devices > 0 or bool(o.devices):
         raise ValueError("Frame.denoise needs a whole frame: not sharded, not compact")
@@ -587,4 +599,22 @@ def _frame_denoise(self, demodulate: bool = True, **opts) -> np.ndarray:
                    **opts)
 
 
+def _frame_denoise_device(self, out_ptr: int, stream: int = 0, demodulate: bool = True, **opts):
+    """denoise(resident=True) into caller-owned device memory (ny * nx * 3 floats, e.g. a torch tensor's
+    data_ptr), enqueued behind `stream`; synchronous on return (rtg_frame_denoise_device)."""
+    do = _denoise_opts(**opts)
+    A.check(self.lib.rtg_frame_denoise_device(self.handle, C.byref(do), int(bool(demodulate)), C.c_void_p(out_ptr),
+                                              C.c_void_p(stream)), self.lib)
+
+
+def _frame_guides_device(self, rgb: int = 0, normal: int = 0, depth: int = 0, albedo: int = 0, variance: int = 0,
+                         stream: int = 0):
+    """Copy what the resident filter reads at the frame's current state into caller-owned device arrays
+    (raw pointers, 0 = not wanted): rgb, normal, albedo (ny * nx * 3 floats), depth, variance (ny * nx)."""
+    g = A.FrameGuides(*(C.c_void_p(p or None) for p in (rgb, normal, depth, albedo, variance)))
+    A.check(self.lib.rtg_frame_guides_device(self.handle, C.byref(g), C.c_void_p(stream)), self.lib)
+
+
 Frame.denoise = _frame_denoise
+Frame.denoise_device = _frame_denoise_device
+Frame.guides_device = _frame_guides_device
