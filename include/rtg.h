@@ -734,6 +734,36 @@ int32_t rtg_frame_denoise_device(rtg_frame* frame, const rtg_denoise_opts* opts,
    fewer than two samples): RTG_ERR_INVALID. */
 int32_t rtg_frame_guides_device(rtg_frame* frame, const rtg_frame_guides* out_device, void* stream);
 
+/* ---- ABI 10 additions: occlusion queries and ray queries on device arrays -----
+   Additive: the version stays 10, no struct grows.
+
+   rtg_trace_occluded answers "is anything in front of tmax?" for a batch of rays: occluded[i] = 1 iff
+   rtg_trace_closest would report, for the same ray, time and scene, full != 0 and t < tmax[i] (t is
+   rtg_hit.t: with an unnormalised direction both are in units of the ray parameter); else 0.  tmax NULL
+   means +inf for every ray; a tmax that is NaN, zero or negative gives 0, and so does a ray with a NaN
+   origin or direction.  traversal 0 (pruned) stops a ray at the first top-level entry that settles its
+   answer; traversal 1 (exhaustive) runs the reference's whole loop and compares afterwards.  Both give
+   the same bytes.
+
+   The _device forms take device arrays on the scene's device -- rays as rtg_ray records (28 B), hits as
+   rtg_hit records (44 B), one byte per ray for the occlusion -- and are enqueued on `stream`
+   (hipStream_t); synchronous on return.  They copy nothing to the host.  Their workspace (the rays as
+   planes and one 16-byte hit record per ray: 44 B per ray) is kept on the scene, grows to the largest n
+   seen, is released by rtg_scene_destroy and is shared with no render, frame or feature-buffer call: a
+   query between two renders or two rtg_frame_add_samples changes no bit of theirs.  Once it is large
+   enough a call allocates nothing.  rtg_trace_occluded stages its host arrays in device memory for the
+   call (33 B per ray) and uses the same workspace.  Two concurrent calls on one scene are as unsupported
+   as two renders are.
+
+   Checked in this order: NULL scene, n < 0, or a NULL rays / hits / occluded array with n > 0
+   (RTG_ERR_INVALID); n == 0 (RTG_OK, nothing touched); a host-only scene (RTG_ERR_NO_DEVICE). */
+int32_t rtg_trace_occluded(rtg_scene* scene, const rtg_ray* rays, const float* tmax, int32_t n,
+                           uint8_t* occluded, int32_t traversal);
+int32_t rtg_trace_closest_device(rtg_scene* scene, const rtg_ray* rays_device, int32_t n,
+                                 rtg_hit* hits_device, int32_t traversal, void* stream);
+int32_t rtg_trace_occluded_device(rtg_scene* scene, const rtg_ray* rays_device, const float* tmax_device,
+                                  int32_t n, uint8_t* occluded_device, int32_t traversal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

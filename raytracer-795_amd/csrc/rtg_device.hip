@@ -798,7 +798,7 @@ DEV void visit_object(const SceneView& sv, const int i, const f3 o, const f3 d, 
 // group's entries in the object loop.
 // STATS: lane work / slots in st.gwork / st.gslot; wave cycles of the set-up (transform, reciprocals,
 // window: up to the first triangle) and of the tests charged to ecyc[16] / ecyc[17].
-template <bool STATS = false>
+template <bool STATS = false, bool ANYHIT = false>   // ANYHIT: closest_hit's entry-level exit (lane_done)
 DEV bool flat_group(const SceneView& sv, const f3 o, const f3 d, const float time, float& nearest, HitRec& out,
                     Stats& st, unsigned long long* ecyc) {
     const unsigned long long c0 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -911,16 +911,16 @@ DEV bool flat_group(const SceneView& sv, const f3 o, const f3 d, const float tim
     }
     if (!perlane) {
         unsigned mm = un;                           // every lane skips the members it has no candidate in
-        while (mm) {
+        while (mm && !wave_done<ANYHIT>(out)) {
             const int e = __builtin_ctz(mm);
             mm &= mm - 1u;
             const GroupEnt& G = sv.gents[e];
             const unsigned m = (cand >> G.first) & ((1u << G.count) - 1u);
-            if (m) member(G, m);
+            if (m && !lane_done<ANYHIT>(out)) member(G, m);
         }
     } else {
         unsigned mm = cm;
-        while (mm) {
+        while (mm && !lane_done<ANYHIT>(out)) {
             const int e = __builtin_ctz(mm);
             mm &= mm - 1u;
             const GroupEnt& G = sv.gents[e];
@@ -936,8 +936,8 @@ DEV bool flat_group(const SceneView& sv, const f3 o, const f3 d, const float tim
 #endif
 // ecyc (STATS): per-entry wave-cycle accumulators in LDS (the kernel flushes them to Counters); the
 // flat group's cycles are charged to slot 15
-// BDIST (the path tracer's shadow queries): the bounding sphere's parameter test too (below)
-template <bool EXHAUSTIVE, bool STATS, bool TLAS = false, bool UNI = false, bool BDIST = false>
+// BDIST (the path tracer's shadow queries): the bounding sphere's parameter test too (below); ANYHIT: lane_done
+template <bool EXHAUSTIVE, bool STATS, bool TLAS = false, bool UNI = false, bool BDIST = false, bool ANYHIT = false>
 DEV HitRec closest_hit(const SceneView& sv, f3 o, f3 d, float time, float tmax, int* stack, int sstride, Stats& st,
                        short* tstack = nullptr, bool uni = false, unsigned long long* ecyc = nullptr) {
     HitRec out;
@@ -962,14 +962,14 @@ DEV HitRec closest_hit(const SceneView& sv, f3 o, f3 d, float time, float tmax, 
         bool grouped = false;
         if (!EXHAUSTIVE && sv.num_gents > 0 && __ballot(fin) != 0ull) {
             const unsigned long long c0 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
-            if (fin) grouped = flat_group<STATS>(sv, o, d, time, nearest, out, st, ecyc);
+            if (fin) grouped = flat_group<STATS, ANYHIT>(sv, o, d, time, nearest, out, st, ecyc);
             if (STATS && ecyc && (__ballot(1) & __lanemask_lt()) == 0ull)
                 atomicAdd(ecyc + 15, __builtin_amdgcn_s_memtime() - c0);
         }
-        for (int i = 0; i < sv.num_tops; i++) {
+        for (int i = 0; !(ANYHIT && wave_done<ANYHIT>(out)) && i < sv.num_tops; i++) {   // (constant first: folds)
             if (STATS) st.considered++;
             const unsigned long long c0 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
-            bool skip = grouped && sv.tops[i].grouped;
+            bool skip = (grouped && sv.tops[i].grouped) || lane_done<ANYHIT>(out);
             if (!skip && !EXHAUSTIVE && sv.tops[i].wbox && wfast && tin) {
                 const TopObject& T = sv.tops[i];
                 const f3 wi = mk(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
@@ -1053,14 +1053,14 @@ DEV HitRec closest_hit(const SceneView& sv, f3 o, f3 d, float time, float tmax, 
     // equal t goes to the lower index in any order.
     int tsp = 0;
     int cur = sv.tlas_root;
-    while (true) {
+    while (!wave_done<ANYHIT>(out)) {
         const Node nd = sv.tlas[cur];
         const bool lpr = !(nd.d.x & kTlasNoPrune), rpr = !(nd.d.y & kTlasNoPrune);
         const int lref = nd.d.x & ~kTlasNoPrune, rref = nd.d.y & ~kTlasNoPrune, lcnt = nd.d.z, rcnt = nd.d.w;
         float lk = 0.0f, rk = 0.0f;
         bool lok = lcnt >= 0 && tchild(nd.a.x, nd.a.y, nd.a.z, nd.a.w, nd.b.x, nd.b.y, lpr, lk);
         bool rok = rcnt >= 0 && tchild(nd.b.z, nd.b.w, nd.c.x, nd.c.y, nd.c.z, nd.c.w, rpr, rk);
-        auto still = [&](float k, bool prune) { return !prune || !beyond(k); };
+        auto still = [&](float k, bool prune) { return !lane_done<ANYHIT>(out) && (!prune || !beyond(k)); };
         const bool lleaf = lcnt > 0, rleaf = rcnt > 0;
         if (lleaf || rleaf) {
             // leaf children, the nearer (for the wave's first lane) first; a lane takes the second
@@ -1075,7 +1075,7 @@ DEV HitRec closest_hit(const SceneView& sv, f3 o, f3 d, float time, float tmax, 
                 for (int k = ref; k < ref + cnt; k++) {
                     const int e = sv.tlas_idx[k];
                     if (STATS) { st.considered++; st.entries += need ? 1u : 0u; }
-                    if (need) visit(e);
+                    if (need && !lane_done<ANYHIT>(out)) visit(e);
                 }
             }
             if (lleaf) lok = false;
@@ -3194,6 +3194,59 @@ __global__ void __launch_bounds__(256) k_hit_details(const SceneView sv, const R
     out[i] = o;
 }
 
+// ------------------------------------------------------------------ ray queries on device arrays
+// AoS rtg_ray records (28 B, the C ABI's layout) -> the RayQ planes the traversal reads, times included.
+__global__ void __launch_bounds__(256) k_pack_rays(const rtg_ray* __restrict__ in, const RayQ q, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* r = reinterpret_cast<const float*>(in) + (size_t)7 * i;
+    q.a[i] = make_float4(r[0], r[1], r[2], r[3]);
+    q.b[i] = make_float2(r[4], r[5]);
+    q.t[i] = r[6];
+}
+
+// Occlusion query: out[i] = 1 iff the closest hit of ray i -- what k_trace reports for it -- exists and
+// has t < tmax[i] (tmax null: +inf; NaN, zero or negative: 0).  The pruned walk is closest_hit with
+// `nearest` starting at the bound and the entry-level exit (ANYHIT): the first accepted entry settles the
+// answer, since nearest only decreases from there.  min(tmax, FLT_MAX) is k_trace's own start, so a bound of
+// +inf accepts exactly what k_trace accepts.  EXHAUSTIVE: the reference's loop to its end, compared afterwards.
+// The exit is per entry, never inside an object's walk: an object's winner can be a candidate within eps
+// behind the origin that hides the object's valid hits, so "some candidate below tmax" is not
+// the contract's answer.
+#ifndef RTG_OCCLUDED_EXIT
+#define RTG_OCCLUDED_EXIT 1         // the entry-level exit (A/B: 0, the bounded walk to its end -- the same bytes)
+#endif
+constexpr int kOccludedBlock = 64;  // one wave per block, as the other traversal kernels (LDS stack: 128 B per lane)
+#define RTG_OCCLUDED_ATTR __attribute__((amdgpu_waves_per_eu(TLAS ? RTG_TLAS_WAVES : RTG_TRAVERSAL_WAVES)))
+template <bool EXHAUSTIVE, bool TLAS>
+__global__ void __launch_bounds__(kOccludedBlock) RTG_OCCLUDED_ATTR k_occluded(const SceneView sv, const RayQ rays,
+                                                                              const float* __restrict__ tmax,
+                                                                              unsigned char* __restrict__ out, int n) {
+    __shared__ int s_stack[kLdsStack * kOccludedBlock];
+    __shared__ short s_tstack[TLAS ? kTlasStack * kOccludedBlock : 1];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 o, d;
+    float time;
+    load_ray(rays, i, o, d, time);
+    const float tm = tmax ? tmax[i] : INFINITY;
+    bool occ = false;
+    if (tm > 0.0f) {        // false for NaN
+        Stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (EXHAUSTIVE) {
+            const HitRec h = closest_hit<true, false, false, false>(sv, o, d, time, FLT_MAX, s_stack + threadIdx.x,
+                                                                    kOccludedBlock, st, s_tstack, false, nullptr);
+            occ = h.obj >= 0 && h.t < tm;
+        } else {
+            const HitRec h = closest_hit<false, false, TLAS, false, false, RTG_OCCLUDED_EXIT != 0>(
+                sv, o, d, time, fminf(tm, FLT_MAX), s_stack + threadIdx.x, kOccludedBlock, st,
+                s_tstack + (TLAS ? threadIdx.x : 0), false, nullptr);
+            occ = h.obj >= 0;
+        }
+    }
+    out[i] = occ ? 1 : 0;
+}
+
 // ------------------------------------------------------------------ launchers
 static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 
@@ -3243,6 +3296,18 @@ void launch_trace(const SceneView& sv, const CameraDev& cam, const PassDevA& ps,
         with_pass(ps, [&](const auto& p) {
             launch_trace_t(sv, io.rays, io.hits, io.n, exhaustive, ctr, st, &cam, p, seed, /*compact=*/true, io.nq, io.gbase);
         });
+}
+void launch_pack_rays(const rtg_ray* rays, const RayQ q, int n, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_pack_rays, dim3(nblk(n, 256)), dim3(256), 0, st, rays, q, n);
+}
+void launch_occluded(const SceneView& sv, const RayQ rays, const float* tmax, unsigned char* out, int n, int exhaustive,
+                     hipStream_t st) {
+    if (n <= 0) return;
+    const dim3 g(nblk(n, kOccludedBlock)), b(kOccludedBlock);
+    if (exhaustive) hipLaunchKernelGGL((k_occluded<true, false>), g, b, 0, st, sv, rays, tmax, out, n);
+    else if (sv.tlas_root >= 0) hipLaunchKernelGGL((k_occluded<false, true>), g, b, 0, st, sv, rays, tmax, out, n);
+    else hipLaunchKernelGGL((k_occluded<false, false>), g, b, 0, st, sv, rays, tmax, out, n);
 }
 __global__ void k_warm() {}
 void device_warm(hipStream_t st) { hipLaunchKernelGGL(k_warm, dim3(1), dim3(64), 0, st); }

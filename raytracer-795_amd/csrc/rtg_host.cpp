@@ -1172,7 +1172,7 @@ struct rtg_scene {
     int num_emit = 0;                        // hw7 object lights
     // render workspace
     std::vector<Lane> lanes;
-    DBuf d_acc, d_counters, d_stats;
+    DBuf d_acc, d_counters, d_stats, d_query;   // d_query: the device-array ray queries' workspace
     DBuf d_rad;                              // stream schedule: per-sample radiance of a segment
     rtg_render_stats stats{};
     int num_lanes = 8;                       // default passes in flight (rtg_render_opts.streams overrides)
@@ -1314,7 +1314,7 @@ static void scene_free(rtg_scene* s) {
     multi_free(s->multi);
     s->multi = nullptr;
     for (DBuf* b : scene_buffers(s)) b->release();
-    s->d_acc.release(); s->d_counters.release(); s->d_stats.release(); s->d_rad.release();
+    s->d_acc.release(); s->d_counters.release(); s->d_stats.release(); s->d_rad.release(); s->d_query.release();
     for (Lane& l : s->lanes) l.destroy();
     s->lanes.clear();
 }
@@ -4057,6 +4057,100 @@ int32_t rtg_trace_closest(rtg_scene* s, const rtg_ray* rays, int32_t n, rtg_hit*
         dr.release(); dh.release(); dout.release();
         if (e != hipSuccess) return fail(RTG_ERR_HIP, std::string("trace: ") + hipGetErrorString(e));
         return RTG_OK;
+    });
+}
+
+// ---- ray queries on device arrays
+// The queries' workspace, kept on the scene and grown only: the rays as RayQ planes with times (what the
+// traversal reads), then one HitRec per ray.  It is the queries' own: no render, frame or AOV buffer is used.
+struct QueryWs {
+    RayQ q;
+    HitRec* hits;
+};
+static int query_workspace(rtg_scene* s, int n, QueryWs& w) {
+    const size_t planes = (kRayBytes * (size_t)n + 15) & ~(size_t)15;
+    const int rc = s->d_query.grow(planes + sizeof(HitRec) * (size_t)n);
+    if (rc) return rc;
+    w.q = ray_planes(s->d_query.p, n, true);
+    w.hits = reinterpret_cast<HitRec*>(static_cast<char*>(s->d_query.p) + planes);
+    return RTG_OK;
+}
+// the argument rules shared by the queries: INVALID, then n == 0 (done: *done set), then NO_DEVICE
+static int query_args(const rtg_scene* s, int32_t n, bool arrays, bool* done) {
+    *done = false;
+    if (!s || n < 0 || (n && !arrays)) return fail(RTG_ERR_INVALID, "bad arguments");
+    if (n == 0) { *done = true; return RTG_OK; }
+    if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot trace");
+    return RTG_OK;
+}
+static int query_finish(hipStream_t st, const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(RTG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return RTG_OK;
+}
+static int occluded_on_device(rtg_scene* s, const rtg_ray* rays, const float* tmax, int32_t n, uint8_t* occluded,
+                              int32_t traversal, hipStream_t st) {
+    QueryWs w;
+    const int rc = query_workspace(s, n, w);
+    if (rc) return rc;
+    launch_pack_rays(rays, w.q, n, st);
+    launch_occluded(s->sv, w.q, tmax, occluded, n, traversal == 1, st);
+    return query_finish(st, "trace occluded");
+}
+
+int32_t rtg_trace_closest_device(rtg_scene* s, const rtg_ray* rays, int32_t n, rtg_hit* hits, int32_t traversal,
+                                 void* stream) {
+    return guarded([&]() -> int32_t {
+        bool done;
+        const int rc0 = query_args(s, n, rays && hits, &done);
+        if (rc0 || done) return rc0;
+        HIP_TRY(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        QueryWs w;
+        const int rc = query_workspace(s, n, w);
+        if (rc) return rc;
+        launch_pack_rays(rays, w.q, n, st);
+        launch_trace_queued(s->sv, w.q, w.hits, n, traversal == 1, st);
+        launch_hit_details(s->sv, w.q, w.hits, hits, s->d_origprim.as<int>(), n, st);
+        return query_finish(st, "trace closest");
+    });
+}
+
+int32_t rtg_trace_occluded_device(rtg_scene* s, const rtg_ray* rays, const float* tmax, int32_t n, uint8_t* occluded,
+                                  int32_t traversal, void* stream) {
+    return guarded([&]() -> int32_t {
+        bool done;
+        const int rc0 = query_args(s, n, rays && occluded, &done);
+        if (rc0 || done) return rc0;
+        HIP_TRY(hipSetDevice(s->device));
+        return occluded_on_device(s, rays, tmax, n, occluded, traversal, (hipStream_t)stream);
+    });
+}
+
+int32_t rtg_trace_occluded(rtg_scene* s, const rtg_ray* rays, const float* tmax, int32_t n, uint8_t* occluded,
+                           int32_t traversal) {
+    return guarded([&]() -> int32_t {
+        bool done;
+        const int rc0 = query_args(s, n, rays && occluded, &done);
+        if (rc0 || done) return rc0;
+        HIP_TRY(hipSetDevice(s->device));
+        // one staging allocation: the rays, the bounds, the answers
+        const size_t nr = sizeof(rtg_ray) * (size_t)n, nt = sizeof(float) * (size_t)n;
+        DBuf stage;
+        int rc = stage.grow(nr + nt + (size_t)n);
+        if (rc) return rc;
+        char* base = stage.as<char>();
+        float* dtmax = tmax ? reinterpret_cast<float*>(base + nr) : nullptr;
+        uint8_t* docc = reinterpret_cast<uint8_t*>(base + nr + nt);
+        hipError_t e = hipMemcpy(base, rays, nr, hipMemcpyHostToDevice);
+        if (e == hipSuccess && tmax) e = hipMemcpy(dtmax, tmax, nt, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = fail(RTG_ERR_HIP, std::string("trace occluded upload: ") + hipGetErrorString(e));
+        if (!rc) rc = occluded_on_device(s, reinterpret_cast<const rtg_ray*>(base), dtmax, n, docc, traversal, nullptr);
+        if (!rc && (e = hipMemcpy(occluded, docc, (size_t)n, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = fail(RTG_ERR_HIP, std::string("trace occluded download: ") + hipGetErrorString(e));
+        stage.release();
+        return rc;
     });
 }
 

@@ -485,6 +485,28 @@ void launch_trace(const SceneView& sv, const CameraDev& cam, const PassDevA& ps,
                   int exhaustive, Counters* ctr, hipStream_t st);
 // queued rays only, full hit records (rtg_trace_closest): no camera, no pass
 void launch_trace_queued(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, hipStream_t st);
+// ray queries on device arrays: n AoS rtg_ray records -> RayQ planes with times; out[i] = 1 iff
+// ray i's closest hit has t < tmax[i] (tmax null: +inf), one byte per ray
+void launch_pack_rays(const struct ::rtg_ray* rays, const RayQ q, int n, hipStream_t st);
+void launch_occluded(const SceneView& sv, const RayQ rays, const float* tmax, unsigned char* out, int n, int exhaustive,
+                     hipStream_t st);
+// workspace of a device-array query per ray: the ray planes (kRayBytes) and a HitRec
+constexpr size_t kQueryBytes = kRayBytes + 16;
+#ifdef __HIPCC__
+// closest_hit's ANYHIT flag (occlusion queries, k_occluded): the caller asks only whether the closest hit lies
+// below tmax.  `nearest` starts at tmax and only decreases, and the top-level acceptance is strict, so a lane
+// that has accepted an entry (h.obj >= 0) knows the answer whatever the remaining entries hold: it is done and
+// skips them, and a loop ends when its wave has no undone lane left.  With the flag off (every other kernel)
+// both are the constant false: those walks compile to what they were.
+template <bool ANYHIT> __device__ __forceinline__ bool lane_done(const HitRec& h) {
+    if constexpr (ANYHIT) return h.obj >= 0;
+    else return false;
+}
+template <bool ANYHIT> __device__ __forceinline__ bool wave_done(const HitRec& h) {
+    if constexpr (ANYHIT) return __ballot(h.obj < 0) == 0ull;
+    else return false;
+}
+#endif
 void launch_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
                   hipStream_t st);
 void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,

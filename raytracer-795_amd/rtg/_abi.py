@@ -276,6 +276,11 @@ EXPORTS = {
     "rtg_frame_denoise": (C.c_int32, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_int32, PF]),
     "rtg_frame_denoise_device": (C.c_int32, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_int32, C.c_void_p, C.c_void_p]),
     "rtg_frame_guides_device": (C.c_int32, [C.c_void_p, C.POINTER(FrameGuides), C.c_void_p]),
+    # ABI 10 additions: occlusion queries and ray queries on device arrays
+    "rtg_trace_occluded": (C.c_int32, [C.c_void_p, C.POINTER(Ray), PF, C.c_int32, C.POINTER(C.c_uint8), C.c_int32]),
+    "rtg_trace_closest_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtg_trace_occluded_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_void_p]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -618,3 +618,48 @@ def _frame_guides_device(self, rgb: int = 0, normal: int = 0, depth: int = 0, al
 Frame.denoise = _frame_denoise
 Frame.denoise_device = _frame_denoise_device
 Frame.guides_device = _frame_guides_device
+
+
+# ---------------------------------------------------------------------------- ray queries
+def _renderer_occluded(self, origins, directions, tmax=None, times=None, traversal: int = 0) -> np.ndarray:
+    """Occlusion query (rtg_trace_occluded): a bool per ray, True iff trace() reports a hit with t < tmax for
+    it.  `tmax`: None (+inf), a scalar or one value per ray, in trace()'s `t` units; NaN, 0 or negative: False."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    n = len(o)
+    rays = (A.Ray * max(n, 1))()
+    buf = np.frombuffer(rays, dtype=np.float32, count=7 * max(n, 1)).reshape(-1, 7)
+    buf[:n, 0:3], buf[:n, 3:6] = o, d
+    buf[:n, 6] = 0 if times is None else np.asarray(times, np.float32)
+    tm = None
+    if tmax is not None:
+        tm = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+    out = np.zeros(max(n, 1), np.uint8)
+    A.check(self.lib.rtg_trace_occluded(self.handle, rays, None if tm is None else tm.ctypes.data_as(A.PF), n,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint8)), int(traversal)), self.lib)
+    return out[:n] != 0
+
+
+def _renderer_trace_device(self, rays_ptr: int, n: int, hits_ptr: int, stream: int = 0, traversal: int = 0):
+    """trace() on caller-owned device arrays (rtg_trace_closest_device), enqueued on `stream`, synchronous on
+    return.  The torch shapes that carry the C layouts: rays a contiguous float32 (n, 7) tensor (rtg_ray, 28 B:
+    origin, direction, time), hits an int32 (n, 11) tensor (rtg_hit, 44 B: full, object, prim, material, then
+    t, point, normal in columns 4..10, to be viewed as float32); pass their data_ptr().  hits_to_dict reads
+    the host copy: hits_to_dict(hits.cpu().numpy(), n)."""
+    A.check(self.lib.rtg_trace_closest_device(self.handle, C.c_void_p(rays_ptr or None), int(n),
+                                              C.c_void_p(hits_ptr or None), int(traversal), C.c_void_p(stream)),
+            self.lib)
+
+
+def _renderer_occluded_device(self, rays_ptr: int, n: int, out_ptr: int, tmax_ptr: int = 0, stream: int = 0,
+                              traversal: int = 0):
+    """occluded() on caller-owned device arrays (rtg_trace_occluded_device): rays as for trace_device, `out` a
+    uint8 (n,) tensor (1 = occluded), `tmax` a float32 (n,) tensor or 0 for +inf."""
+    A.check(self.lib.rtg_trace_occluded_device(self.handle, C.c_void_p(rays_ptr or None), C.c_void_p(tmax_ptr or None),
+                                               int(n), C.c_void_p(out_ptr or None), int(traversal),
+                                               C.c_void_p(stream)), self.lib)
+
+
+Renderer.occluded = _renderer_occluded
+Renderer.trace_device = _renderer_trace_device
+Renderer.occluded_device = _renderer_occluded_device

@@ -17,7 +17,7 @@ for unit in ('rtg_device', 'rtg_denoise'):
     # amdhsa metadata blocks: one per kernel
     for blk in s.split('  - .agpr_count')[1:]:
         name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-        if not re.search(r'k_(trace|shadow|shade|pt_shade|aov|dn|frame_inputs)', name):
+        if not re.search(r'k_(trace|shadow|shade|pt_shade|aov|dn|frame_inputs|occluded|pack_rays)', name):
             continue
         g = lambda k: (re.search(r'\.' + k + r':\s+(\d+)', blk) or [0, '?'])[1]
         dem = re.sub(r'_ZN3rtg(\d+_GLOBAL__N_1)?', '', name)[:60]
