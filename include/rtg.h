@@ -764,6 +764,42 @@ int32_t rtg_trace_closest_device(rtg_scene* scene, const rtg_ray* rays_device, i
 int32_t rtg_trace_occluded_device(rtg_scene* scene, const rtg_ray* rays_device, const float* tmax_device,
                                   int32_t n, uint8_t* occluded_device, int32_t traversal, void* stream);
 
+/* ---- ABI 10 additions: updating a built scene in place --------------------------
+   Additive: the version stays 10, no struct grows.
+
+   rtg_scene_update re-derives the top level of a built scene -- entries, world bounds, top-level BVH, flat
+   group, materials, lights -- from a whole descriptor, without touching what was built per object (smooth
+   normals, both trees of every mesh, the triangle records).  The descriptor has a frozen part, which must
+   equal the build's, and a free part, which may change.
+
+   Frozen: vertices, texcoords, faces, every texture's texels and every other field of the texture table;
+   intersection_test_eps; per object type, id, center, radius, v, face_first, face_count, smooth,
+   num_textures, textures, texture_offset, is_light, radiance; per instance base_object and id; num_objects,
+   num_instances, num_vertices, num_texcoords, num_faces, num_textures, num_materials.  The frozen arrays
+   (vertices, texcoords, faces, texels) may be NULL, meaning "as built": they are never read.
+   Free: the four transformation tables and xform_refs with their counts; per object and instance
+   xform_first, xform_count, blur, material, and an instance's reset_transform; materials; lights and
+   num_lights (with the object lights at most 64); environment_light, background_texture, background,
+   ambient_light, shadow_ray_eps, max_recursion_depth.
+
+   After RTG_OK every call on the scene gives, bit for bit, what it gives on a scene freshly created on the
+   same device with the same build options from the build's frozen part joined with desc's free part.
+   Updates compose.  rtg_scene_build_stats then reports tlas_nodes, flat_group_entries, top_level_ms,
+   upload_ms, upload_bytes and total_ms of the update alone; the other fields stay as built.
+
+   Checked in this order, before anything is touched: NULL scene or desc (RTG_ERR_INVALID); a scene with
+   live frames (RTG_ERR_INVALID: a frame's accumulator and cached guides belong to the scene it was made
+   on); the descriptor checks of rtg_scene_create (RTG_ERR_INVALID); a changed frozen field
+   (RTG_ERR_UNSUPPORTED, the message names it).  A failure after that leaves the scene unusable for
+   everything but rtg_scene_destroy, and the message says so.  A host-only scene updates too.  Calls on one
+   scene must not be concurrent. */
+int32_t rtg_scene_update(rtg_scene* scene, const rtg_scene_desc* desc);
+/* A 64-bit FNV-1a hash of the host images of everything the top-level phases produce, as uploaded (the
+   arrays in a fixed order, then the scalars of the kernels' view: DESIGN.md §24), computed at the end of
+   rtg_scene_create and rtg_scene_update; host-only scenes have it too.  Equal descriptors give equal
+   hashes: an updated scene can be held against a fresh one without rendering. */
+int32_t rtg_scene_top_hash(const rtg_scene* scene, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

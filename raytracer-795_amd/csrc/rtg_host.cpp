@@ -1170,8 +1170,8 @@ struct rtg_scene {
     int tlas_count = 0;                      // its nodes
     float tlas_k[3] = {0, 0, 0};             // per axis: bound of |object-space coordinate x scale| over aligned entries
     int num_emit = 0;                        // hw7 object lights
-    // render workspace
-    std::vector<Lane> lanes;
+    SceneUpdate up;                          // rtg_scene_update: the kept inputs and its state
+    std::vector<Lane> lanes;                 // render workspace (with the buffers below)
     DBuf d_acc, d_counters, d_stats, d_query;   // d_query: the device-array ray queries' workspace
     DBuf d_rad;                              // stream schedule: per-sample radiance of a segment
     rtg_render_stats stats{};
@@ -1211,10 +1211,10 @@ int32_t rtg_device_count(void) {
     return n;
 }
 
-static int validate(const rtg_scene_desc* d) {
+static int validate(const rtg_scene_desc* d, bool as_built = false) {   // as_built (rtg_scene_update): frozen arrays may be null, unread
     if (!d) return fail(RTG_ERR_INVALID, "null scene descriptor");
     if (d->abi_version != RTG_ABI_VERSION) return fail(RTG_ERR_INVALID, "abi_version mismatch");
-    if (d->num_vertices < 0 || (d->num_vertices && !d->vertices)) return fail(RTG_ERR_INVALID, "bad vertices");
+    if (d->num_vertices < 0 || (d->num_vertices && !d->vertices && !as_built)) return fail(RTG_ERR_INVALID, "bad vertices");
     if (d->num_objects < 0 || (d->num_objects && !d->objects)) return fail(RTG_ERR_INVALID, "bad objects");
     if (d->num_lights > kMaxLights) return fail(RTG_ERR_UNSUPPORTED, "more than 64 lights");
     auto vok = [&](int v) { return v >= 1 && v <= d->num_vertices; };
@@ -1245,7 +1245,7 @@ static int validate(const rtg_scene_desc* d) {
         } else if (o.type == RTG_OBJ_MESH) {
             if (o.face_first < 0 || o.face_count < 0 || o.face_first + o.face_count > d->num_faces)
                 return fail(RTG_ERR_INVALID, "mesh face range");
-            for (int f = 0; f < o.face_count; f++)
+            for (int f = 0; f < o.face_count && !as_built; f++)
                 for (int q = 0; q < 3; q++)
                     if (!vok(d->faces[3 * (o.face_first + f) + q])) return fail(RTG_ERR_INVALID, "mesh face index");
         } else {
@@ -1260,7 +1260,7 @@ static int validate(const rtg_scene_desc* d) {
     }
     for (int i = 0; i < d->num_textures; i++) {
         const rtg_texture_desc& t = d->textures[i];
-        if (t.kind == RTG_TEX_IMAGE && (t.width < 1 || t.height < 1 || !t.texels))
+        if (t.kind == RTG_TEX_IMAGE && (t.width < 1 || t.height < 1 || (!t.texels && !as_built)))
             return fail(RTG_ERR_INVALID, "image texture without texels");
     }
     for (int i = 0; i < d->num_lights; i++)
@@ -1314,7 +1314,7 @@ static void scene_free(rtg_scene* s) {
     multi_free(s->multi);
     s->multi = nullptr;
     for (DBuf* b : scene_buffers(s)) b->release();
-    s->d_acc.release(); s->d_counters.release(); s->d_stats.release(); s->d_rad.release(); s->d_query.release();
+    s->d_acc.release(); s->d_counters.release(); s->d_stats.release(); s->d_rad.release(); s->d_query.release(); (void)hipFree(s->up.d_radius); s->up.d_radius = nullptr;
     for (Lane& l : s->lanes) l.destroy();
     s->lanes.clear();
 }
@@ -1484,8 +1484,8 @@ struct SceneArrays {
     hvec<float> gates;                       // per reference position: its leaf's parent box
     hvec<TriGeom> tris;
     hvec<int4> primidx;
-    std::vector<int> pos_leaf;               // per reference position: first position of its leaf ...
-    std::vector<char> pos_gated;             // ... and whether its leaf's parent (gates[]) is not the root
+    SmallMeshes small;                       // the flat group's candidates (leaf_gates); like geoms, geom_finite and emit
+    std::vector<EmitSource> emit;            // (the object lights' corners) kept by the scene for rtg_scene_update
     std::vector<char> geom_finite;           // per object: every primitive box coordinate finite
 
     std::vector<TopObject> tops;
@@ -1554,24 +1554,24 @@ void prepare_geometry(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
         else A.prims[i] = {o.center, 0, 0};
     }
 
-    // matrices (objects, then instances)
-    std::vector<Mat4>& model = A.model;
-    model.resize(d->num_objects);
-    s->inv.clear(); s->invT.clear();
+    // the object lights' corners in object space: object_lights reads them, in a build and in an
+    // update (a sphere's primitive list starts with its centre)
     for (int i = 0; i < d->num_objects; i++) {
-        model[i] = compose(d, d->objects[i].xform_first, d->objects[i].xform_count);
-        s->inv.push_back(inverse(model[i]));
-        s->invT.push_back(inverse_transpose(model[i]));
-        A.top_model.push_back(model[i]);
+        const rtg_object_desc& o = d->objects[i];
+        if (!o.is_light) continue;
+        EmitSource e{i, {}};
+        const size_t nc = o.type == RTG_OBJ_SPHERE ? 1 : A.prims[i].size() / 3 * 3;
+        for (size_t k = 0; k < nc; k++) {
+            const V3 p = verts[A.prims[i][k] - 1];
+            e.corners.insert(e.corners.end(), {p.x, p.y, p.z});
+        }
+        A.emit.push_back(std::move(e));
     }
-    for (int i = 0; i < d->num_instances; i++) {
-        const rtg_instance_desc& in = d->instances[i];
-        Mat4 m = compose(d, in.xform_first, in.xform_count);
-        if (!in.reset_transform) m = mul(m, model[in.base_object]);
-        s->inv.push_back(inverse(m));
-        s->invT.push_back(inverse_transpose(m));
-        A.top_model.push_back(m);
-    }
+
+    // matrices (objects, then instances): a function of the transformation tables alone, which
+    // rtg_scene_update runs again (compose_matrices is defined with it, below)
+    void compose_matrices(rtg_scene * s, const rtg_scene_desc* d, SceneArrays& A);
+    compose_matrices(s, d, A);
 
     // smooth vertex normals (src/Scene.cpp:302-318)
     std::vector<V3>& vn = A.vn;
@@ -1875,8 +1875,8 @@ void linearise_nodes(hvec<Node>& dnodes, ObjWork& w, const ObjBVH& ob, const Geo
 
 // Reference records: the reference leaf of every position: its first position (tie order) and the
 // box of the interior node above it, which gates it (none under the root: closest_hit tests the
-// root); the rows of a small mesh are kept in pos_leaf / pos_gated for the flat group.
-void leaf_gates(SceneArrays& A, ObjWork& w, const ObjBVH& ob, const Geometry& g) {
+// root); the rows of a small mesh (object `obj`) are kept, with its records, for the flat group (SmallMeshes).
+void leaf_gates(SceneArrays& A, ObjWork& w, const ObjBVH& ob, const Geometry& g, int obj) {
     const int np = w.np;
     const hvec<HNode>& hn = ob.nodes;
     hvec<float>& gates = A.gates;
@@ -1906,12 +1906,12 @@ void leaf_gates(SceneArrays& A, ObjWork& w, const ObjBVH& ob, const Geometry& g)
         }
       }
     });
-    if (np <= kFlatMaxPrims) {                  // small meshes: kept for the flat group
-        std::vector<int>& pos_leaf = A.pos_leaf;
-        std::vector<char>& pos_gated = A.pos_gated;
-        pos_leaf.resize(std::max(pos_leaf.size(), (size_t)(g.prim_base + np)), 0);
-        pos_gated.resize(std::max(pos_gated.size(), (size_t)(g.prim_base + np)), 0);
-        for (int k = 0; k < np; k++) { pos_leaf[g.prim_base + k] = leaf_start[k]; pos_gated[g.prim_base + k] = gated[k]; }
+    if (np <= kFlatMaxPrims && w.o.type != RTG_OBJ_SPHERE) {    // small meshes: kept for the flat group
+        SmallMeshes& sm = A.small;
+        sm.first[obj] = (int)sm.tris.size();
+        sm.tris.insert(sm.tris.end(), A.tris.begin() + g.prim_base, A.tris.begin() + g.prim_base + np);
+        sm.pos_leaf.insert(sm.pos_leaf.end(), leaf_start.begin(), leaf_start.end());
+        sm.pos_gated.insert(sm.pos_gated.end(), gated.begin(), gated.end());
     }
 }
 
@@ -2040,7 +2040,7 @@ int build_object(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A, int i, P
     Geometry& g = A.geoms[i];
     reference_primitives(s, A, w, ob, g);
     linearise_nodes(A.dnodes, w, ob, g);
-    leaf_gates(A, w, ob, g);
+    leaf_gates(A, w, ob, g, i);
     // traversal tree (SAH, 4-wide) of a triangle object with an interior reference root and
     // finite primitives (its boxes must bound every candidate; NaN / inf objects keep the
     // reference-tree walk)
@@ -2135,9 +2135,18 @@ void top_level_entries(const rtg_scene* s, const rtg_scene_desc* d, SceneArrays&
 // (squared) for its own rounding and the object-space line's (far origins: a skipped line has
 // |oc| > r, so that slack is >= 1e-5 |oc|, above the transform's ~2e-7 cond |o|); taken only for a
 // well-conditioned matrix and a sphere of at most 60 % of the box's volume.
-void entry_bounding_sphere(TopObject& T, const Mat4& M, const HNode& rt, const Geometry& gg, const hvec<TriGeom>& tris) {
+//
+// The corner pass (corner_radius2, defined with rtg_scene_update below) runs tri_radius2 (rtg_internal.h)
+// over the host's records where the host has them -- a scene build, a host-only scene, a small mesh -- and
+// else on the device over d_tris (rtg_radius.hip: an update of a device scene, whose large meshes' records
+// are not kept on the host).  Both give the same bits: one function, IEEE double add and multiply without
+// contraction on both sides, and a NaN-wins maximum that does not depend on the order of its operands.
+// rtg_scene_create always takes the host pass, over its own arrays.
+int corner_radius2(rtg_scene* s, const SceneArrays& A, int obj, const Geometry& gg, const RadiusXf& X, double* r2);
+
+int entry_bounding_sphere(rtg_scene* s, const SceneArrays& A, TopObject& T, const Mat4& M, const HNode& rt, const Geometry& gg) {
     T.bsph = 0;
-    if (T.wbox && T.kind == 1 && gg.nprims > 0 && gg.prim_base + gg.nprims <= (int)tris.size()) {
+    if (T.wbox && T.kind == 1 && gg.nprims > 0) {
         double fro = 0.0, fri = 0.0;
         for (int c = 0; c < 3; c++)
             for (int r = 0; r < 3; r++) {
@@ -2152,25 +2161,12 @@ void entry_bounding_sphere(TopObject& T, const Mat4& M, const HNode& rt, const G
             for (int r = 0; r < 3; r++) {
                 c0[r] = (double)M.c[0][r] * m[0] + (double)M.c[1][r] * m[1] + (double)M.c[2][r] * m[2] + (double)M.c[3][r];
             }
-            const double r2 = chunk_reduce<double>((size_t)gg.nprims, 65536, 0.0, [&](size_t b0, size_t b1) {
-                double mx2 = 0.0;
-                for (size_t k = (size_t)gg.prim_base + b0; k < (size_t)gg.prim_base + b1; k++) {
-                    const TriGeom& tg = tris[k];
-                    const double a[3] = {tg.p0.x, tg.p0.y, tg.p0.z};
-                    const double e[2][3] = {{tg.p0.w, tg.p1.x, tg.p1.y}, {tg.p1.z, tg.p1.w, tg.p2.x}};
-                    for (int q = 0; q < 3; q++) {
-                        double v[3], d2 = 0.0;
-                        for (int z = 0; z < 3; z++) v[z] = q == 0 ? a[z] : a[z] - e[q - 1][z];
-                        for (int r = 0; r < 3; r++) {
-                            const double w = (double)M.c[0][r] * v[0] + (double)M.c[1][r] * v[1] +
-                                             (double)M.c[2][r] * v[2] + (double)M.c[3][r] - c0[r];
-                            d2 += w * w;
-                        }
-                        mx2 = d2 > mx2 || d2 != d2 ? d2 : mx2;    // NaN propagates (no sphere)
-                    }
-                }
-                return mx2;
-            }, [](double mx2, double v) { return v > mx2 || v != v ? v : mx2; });
+            RadiusXf X;
+            for (int c = 0; c < 4; c++)
+                for (int r = 0; r < 3; r++) X.m[c][r] = (double)M.c[c][r];
+            for (int r = 0; r < 3; r++) X.c0[r] = c0[r];
+            double r2 = 0.0;
+            if (const int rc = corner_radius2(s, A, T.geom, gg, X, &r2)) return rc;
             double bl = 0.0, scale = 0.0, ext = 0.0, vol = 1.0;
             for (int z = 0; z < 3; z++) {
                 bl += (double)T.blur[z] * T.blur[z];
@@ -2188,6 +2184,7 @@ void entry_bounding_sphere(TopObject& T, const Mat4& M, const HNode& rt, const G
             }
         }
     }
+    return RTG_OK;
 }
 
 // world boxes of the transformed entries: the object loop skips such an entry, before its ray
@@ -2195,8 +2192,8 @@ void entry_bounding_sphere(TopObject& T, const Mat4& M, const HNode& rt, const G
 // with a world box and, for axis-aligned ones, the top-level BVH's distance pruning -- behind the
 // origin / beyond the winner so far -- in the object loop: dragon 30.1 -> 31.5, cornell_pt 300 ->
 // 311 ms per frame; not kept.)
-void entry_world_bounds(const rtg_scene* s, const std::vector<Mat4>& top_model, const std::vector<Geometry>& geoms,
-                        const hvec<TriGeom>& tris, std::vector<TopObject>& tops) {
+int entry_world_bounds(rtg_scene* s, const SceneArrays& A, const std::vector<Mat4>& top_model,
+                       const std::vector<Geometry>& geoms, std::vector<TopObject>& tops) {
     for (size_t i = 0; i < tops.size(); i++) {
         TopObject& T = tops[i];
         T.wbox = 0;
@@ -2212,8 +2209,11 @@ void entry_world_bounds(const rtg_scene* s, const std::vector<Mat4>& top_model, 
             fin = fin && std::isfinite(T.wlo[z]) && std::isfinite(T.whi[z]);
         }
         T.wbox = fin ? 1 : 0;
-        entry_bounding_sphere(T, top_model[i], r, geoms[T.geom], tris);
+        if (const int rc = entry_bounding_sphere(s, A, T, top_model[i], r, geoms[T.geom])) return rc;
+        if (T.kind == 1 && getenv("RTG_BUILD_TIMING"))
+            fprintf(stderr, "[rtg] entry %zu: wbox %d bsph %d radius2 %.9g\n", i, T.wbox, T.bsph, T.bsph ? (double)T.bs[3] : 0.0);
     }
+    return RTG_OK;
 }
 
 // top-level BVH over the entries (objects, then instances): replaces the reference's linear
@@ -2222,7 +2222,7 @@ void top_level_bvh(rtg_scene* s, SceneArrays& A) {
     const std::vector<TopObject>& tops = A.tops;
     const std::vector<Mat4>& top_model = A.top_model;
     const std::vector<Geometry>& geoms = A.geoms;
-    s->tlas_root = -1;
+    s->tlas_root = -1; s->tlas_count = 0;
     const int ntops = (int)tops.size();
     const bool want_tlas = s->tlas_mode == 2 ? ntops >= 2 : (s->tlas_mode == 0 && ntops >= kTlasMinEntries);
     for (int z = 0; z < 3; z++) s->tlas_k[z] = 0.0f;
@@ -2262,12 +2262,12 @@ void top_level_bvh(rtg_scene* s, SceneArrays& A) {
 
 // the flat group (GroupEnt, closest_hit), linear-loop scenes only.  (An untransformed object's glm
 // inverse is the identity with signed zeros, so TopObject::ident -- +0 entries only -- is rarely set;
-// the group asks only that its members share one transform.)
+// the group asks only that its members share one transform.)  The candidates' records come from
+// A.small (leaf_gates), which the scene keeps: an update of a device scene has no other host records.
+// (T.grouped is set here on entries that top_level_entries has just cleared: the phase can run again.)
 void flat_group(rtg_scene* s, SceneArrays& A) {
     std::vector<TopObject>& tops = A.tops;
-    const hvec<TriGeom>& tris = A.tris;
-    const std::vector<int>& pos_leaf = A.pos_leaf;
-    const std::vector<char>& pos_gated = A.pos_gated;
+    const SmallMeshes& sm = A.small;
     std::vector<TriGeom>& gtris = A.gtris;
     std::vector<GroupEnt>& gents = A.gents;
     const int ntops = (int)tops.size();
@@ -2288,13 +2288,12 @@ void flat_group(rtg_scene* s, SceneArrays& A) {
         // candidate iff the root box and its leaf's parent box pass the exact slab test (visit_object)
         const ObjBVH& ob = s->bvh[T.geom];
         // (finite only: the gate argument needs every reference box to contain its descendants')
-        if (ob.root < 0 || !A.geom_finite[T.geom] || g.nprims > kFlatMaxPrims ||
-            g.prim_base + g.nprims > (int)pos_leaf.size())
-            continue;
+        const int sf = T.geom < (int)sm.first.size() ? sm.first[T.geom] : -1;
+        if (ob.root < 0 || !A.geom_finite[T.geom] || g.nprims > kFlatMaxPrims || sf < 0) continue;
         std::vector<TriGeom> recs;
-        for (int k = g.prim_base; k < g.prim_base + g.nprims; k++) {
-            TriGeom r = tris[k];
-            set_tri_ref(r, k, pos_leaf[k], (int)pos_gated[k]);
+        for (int k = 0; k < g.nprims; k++) {
+            TriGeom r = sm.tris[sf + k];
+            set_tri_ref(r, g.prim_base + k, sm.pos_leaf[sf + k], (int)sm.pos_gated[sf + k]);
             recs.push_back(r);
         }
         G.root_box = g.node_base >= 0;              // an interior root: its box is tested (a root leaf: none)
@@ -2326,8 +2325,9 @@ void flat_group(rtg_scene* s, SceneArrays& A) {
     s->bst.flat_group_entries = s->num_gents;
 }
 
-// Shading tables: materials, textures and texels, lights.
-void shading_tables(const rtg_scene_desc* d, SceneArrays& A) {
+// Shading tables: materials, textures and texels, lights.  textures = false (rtg_scene_update): the texture
+// table and the texel pool are frozen and stay on the card; A.texs and A.texels are left empty.
+void shading_tables(const rtg_scene_desc* d, SceneArrays& A, bool textures = true) {
     std::vector<MaterialDev>& mats = A.mats;
     mats.resize(d->num_materials);
     for (int i = 0; i < d->num_materials; i++) {
@@ -2341,8 +2341,8 @@ void shading_tables(const rtg_scene_desc* d, SceneArrays& A) {
     }
     std::vector<TextureDev>& texs = A.texs;
     std::vector<float>& texels = A.texels;
-    texs.resize(d->num_textures);
-    for (int i = 0; i < d->num_textures; i++) {
+    texs.resize(textures ? d->num_textures : 0);
+    for (int i = 0; i < d->num_textures && textures; i++) {
         const rtg_texture_desc& t = d->textures[i];
         TextureDev& T = texs[i];
         T.kind = t.kind; T.decal = t.decal; T.interp = t.interp; T.nc = t.noise_conv; T.normalizer = t.normalizer;
@@ -2389,13 +2389,13 @@ void shading_tables(const rtg_scene_desc* d, SceneArrays& A) {
 // hw7 object lights (path tracer NEE): appended after the scene's lights, in object order.
 // World-space geometry sampled at time 0, exactly as oracle/rtg_oracle.c builds it.
 int object_lights(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
-    const std::vector<V3>& verts = A.verts;
     std::vector<float>&etris = A.etris, &ecdf = A.ecdf;
     A.top_emit.assign(d->num_objects + d->num_instances, -1);
     s->num_emit = 0;
-    for (int i = 0; i < d->num_objects; i++) {
+    for (const EmitSource& src : A.emit) {      // the is_light objects, in object order
+        const int i = src.object;
         const rtg_object_desc& o = d->objects[i];
-        if (!o.is_light) continue;
+        auto pv = [&](size_t k) { return v3(src.corners[3 * k], src.corners[3 * k + 1], src.corners[3 * k + 2]); };
         if (d->num_lights + s->num_emit + 1 > kMaxLights) return fail(RTG_ERR_UNSUPPORTED, "more than 64 lights + object lights");
         LightDev L;
         memset(&L, 0, sizeof L);
@@ -2403,18 +2403,18 @@ int object_lights(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
         const Mat4& M = A.model[i];
         if (o.type == RTG_OBJ_SPHERE) {
             L.type = kLightEmitSphere;
-            V3 c = xform_point(M, verts[o.center - 1], 1.0f);
+            V3 c = xform_point(M, pv(0), 1.0f);
             L.pos[0] = c.x; L.pos[1] = c.y; L.pos[2] = c.z;
             L.size = o.radius * vnorm(v3(M.c[0][0], M.c[0][1], M.c[0][2]));
         } else {
             L.type = kLightEmitMesh;
-            const std::vector<int>& pv = A.prims[i];
+            const size_t nc = src.corners.size() / 3;
             L.tri_first = (int)ecdf.size();
-            L.tri_count = (int)(pv.size() / 3);
+            L.tri_count = (int)(nc / 3);
             float acc = 0.0f;
-            for (size_t k = 0; k + 2 < pv.size(); k += 3) {       // parse order
-                V3 a = xform_point(M, verts[pv[k] - 1], 1.0f), b = xform_point(M, verts[pv[k + 1] - 1], 1.0f),
-                   c = xform_point(M, verts[pv[k + 2] - 1], 1.0f);
+            for (size_t k = 0; k + 2 < nc; k += 3) {              // parse order
+                V3 a = xform_point(M, pv(k), 1.0f), b = xform_point(M, pv(k + 1), 1.0f),
+                   c = xform_point(M, pv(k + 2), 1.0f);
                 const float t9[9] = {a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
                 etris.insert(etris.end(), t9, t9 + 9);
                 acc = acc + 0.5f * vnorm(cross(b - a, c - a));
@@ -2429,7 +2429,8 @@ int object_lights(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
     return RTG_OK;
 }
 
-// Upload: the early thread's join and error, then everything it did not upload.
+// Upload: the early thread's join and error, then everything it did not upload (upload_top_level: below).
+int upload_top_level(rtg_scene* s, const SceneArrays& A);
 int upload_scene(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
     A.vflat.assign(d->vertices, d->vertices + 3 * (size_t)d->num_vertices);
     if (d->num_texcoords > 0) A.tcflat.assign(d->texcoords, d->texcoords + 2 * (size_t)d->num_texcoords);
@@ -2437,15 +2438,11 @@ int upload_scene(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
     if (A.early.t.joinable()) A.early.t.join();
     if (A.early_rc != RTG_OK) return fail(A.early_rc, "scene upload (reference-tree records): " + A.early_err);
     if (!A.early_upload && (rc = upload_reference_records(s, A))) return rc;
-    if ((rc = upload(s->d_tops, A.tops)) || (rc = upload(s->d_geoms, A.geoms)) ||
+    if ((rc = upload(s->d_geoms, A.geoms)) ||
         (rc = upload(s->d_nodes4, A.snodes)) || (rc = upload(s->d_stris, A.stris)) ||
         (rc = upload(s->d_vertices, A.vflat)) || (rc = upload(s->d_texcoords, A.tcflat)) ||
-        (rc = upload(s->d_materials, A.mats)) || (rc = upload(s->d_textures, A.texs)) || (rc = upload(s->d_texels, A.texels)) ||
-        (rc = upload(s->d_lights, A.lights)) ||
-        (rc = upload(s->d_topemit, A.top_emit)) || (rc = upload(s->d_etris, A.etris)) || (rc = upload(s->d_ecdf, A.ecdf)) ||
-        (rc = upload(s->d_tlas, A.tlas_nodes)) || (rc = upload(s->d_tlasidx, A.tlas_idx)) ||
-        (rc = upload(s->d_gtris, A.gtris)) || (rc = upload(s->d_gents, A.gents)) || (rc = upload(s->d_gtop, A.gtop)) ||
-        (rc = upload(s->d_tsph, A.tsph)))
+        (rc = upload(s->d_textures, A.texs)) || (rc = upload(s->d_texels, A.texels)) ||
+        (rc = upload_top_level(s, A)))
         return rc;
     s->bst.upload_bytes = 0;
     for (DBuf* b : scene_buffers(s)) s->bst.upload_bytes += b->used;
@@ -2517,6 +2514,8 @@ void derive_view(SceneView& sv, const rtg_scene_desc* d, rtg_scene* s) {
     }
 }
 
+// The end of a build (defined with rtg_scene_update, below): the view, its hash, the frozen copy, the kept inputs.
+void finish_build(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A);
 }  // namespace
 
 extern "C" {
@@ -2533,7 +2532,7 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
 
     // BVHs and device geometry
     A.geoms.resize(d->num_objects);
-    A.geom_finite.assign(d->num_objects, 0);
+    A.geom_finite.assign(d->num_objects, 0); A.small.first.assign(d->num_objects, -1);
     s->orig_prim.clear();
     s->bvh.assign(d->num_objects, ObjBVH());
     int rc;
@@ -2541,19 +2540,20 @@ static int build_scene(rtg_scene* s, const rtg_scene_desc* d) {
         if ((rc = build_object(s, d, A, i, pc))) return rc;
 
     top_level_entries(s, d, A);
-    entry_world_bounds(s, A.top_model, A.geoms, A.tris, A.tops);
+    if ((rc = entry_world_bounds(s, A, A.top_model, A.geoms, A.tops))) return rc;
     top_level_bvh(s, A);
     flat_group(s, A);
     shading_tables(d, A);
     if ((rc = object_lights(s, d, A))) return rc;
     bs.top_level_ms += pc.lap("top_level");
     if (s->device < 0) {                // host-only build (introspection / CPU tests)
+        finish_build(s, d, A);
         s->build_end = std::chrono::steady_clock::now();
         return RTG_OK;
     }
     if ((rc = upload_scene(s, d, A))) return rc;
     bs.upload_ms += pc.lap("upload");
-    derive_view(s->sv, d, s);
+    finish_build(s, d, A);
     pc.lap("view");
     // The host copies of the uploaded records (~300 MB for a 1 M-triangle mesh) are freed by the
     // library's reaper thread (Reaper, above): unmapping them took 18-25 ms of rtg_scene_create on the
@@ -3358,11 +3358,223 @@ static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_rende
     return RTG_OK;
 }
 
+// ------------------------------------------------------------------ rtg_scene_update
+// (Here, below the build, so that the build's lines stay where they are: the build declares what it calls.)
+namespace {
+
+// The composed matrices (objects, then instances): model matrices in A, inverses in the scene.  A function of
+// the transformation tables alone: rtg_scene_update runs it again.
+void compose_matrices(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
+    std::vector<Mat4>& model = A.model;
+    model.resize(d->num_objects);
+    A.top_model.clear();
+    s->inv.clear(); s->invT.clear();
+    for (int i = 0; i < d->num_objects; i++) {
+        model[i] = compose(d, d->objects[i].xform_first, d->objects[i].xform_count);
+        s->inv.push_back(inverse(model[i]));
+        s->invT.push_back(inverse_transpose(model[i]));
+        A.top_model.push_back(model[i]);
+    }
+    for (int i = 0; i < d->num_instances; i++) {
+        const rtg_instance_desc& in = d->instances[i];
+        Mat4 m = compose(d, in.xform_first, in.xform_count);
+        if (!in.reset_transform) m = mul(m, model[in.base_object]);
+        s->inv.push_back(inverse(m));
+        s->invT.push_back(inverse_transpose(m));
+        A.top_model.push_back(m);
+    }
+}
+
+// The host's reference-order records of object `obj` (g.nprims of them): all of them during a build and in a
+// host-only scene, a small mesh's in a device scene's update; null when they are on the device only.
+const TriGeom* host_records(const rtg_scene* s, const SceneArrays& A, int obj, const Geometry& g) {
+    const size_t end = (size_t)g.prim_base + (size_t)g.nprims;
+    if (end <= A.tris.size()) return A.tris.data() + g.prim_base;
+    if (end <= s->up.all_tris.size()) return s->up.all_tris.data() + g.prim_base;
+    const int sf = obj < (int)A.small.first.size() ? A.small.first[obj] : -1;
+    return sf >= 0 ? A.small.tris.data() + sf : nullptr;
+}
+
+// entry_bounding_sphere's corner pass (declared there).
+int corner_radius2(rtg_scene* s, const SceneArrays& A, int obj, const Geometry& gg, const RadiusXf& X, double* r2) {
+    if (const TriGeom* recs = host_records(s, A, obj, gg)) {
+        *r2 = chunk_reduce<double>((size_t)gg.nprims, 65536, 0.0, [&](size_t b0, size_t b1) {
+            double mx2 = 0.0;
+            for (size_t k = b0; k < b1; k++) mx2 = tri_radius2(recs[k], X, mx2);
+            return mx2;
+        }, [](double mx2, double v) { return radius2_fold(mx2, v); });
+        return RTG_OK;
+    }
+    if (s->device < 0 || (size_t)gg.prim_base + (size_t)gg.nprims > s->d_tris.used / sizeof(TriGeom))
+        return fail(RTG_ERR_INVALID, "internal: no triangle records for an entry's bounding sphere");
+    if (!s->up.d_radius && hipMalloc((void**)&s->up.d_radius, sizeof(double) * kRadiusPartials) != hipSuccess) {
+        s->up.d_radius = nullptr;
+        return fail(RTG_ERR_OOM, "hipMalloc failed (radius partials)");
+    }
+    int rc;
+    std::string err;
+    float ms = 0.0f;
+    const bool timed = getenv("RTG_BUILD_TIMING") != nullptr;
+    if ((rc = entry_radius2_device(s->d_tris.as<TriGeom>() + gg.prim_base, gg.nprims, X, s->up.d_radius, r2,
+                                   timed ? &ms : nullptr, err)))
+        return fail(rc, err);
+    if (timed) fprintf(stderr, "[rtg] radius_kernel object %d: %d prims %.4f ms\n", obj, gg.nprims, ms);
+    return RTG_OK;
+}
+
+// The device buffers the top-level phases fill: what rtg_scene_update uploads again.
+std::vector<DBuf*> top_level_buffers(rtg_scene* s) {
+    return {&s->d_tops, &s->d_tsph, &s->d_tlas, &s->d_tlasidx, &s->d_gtris, &s->d_gents, &s->d_gtop,
+            &s->d_materials, &s->d_lights, &s->d_topemit, &s->d_etris, &s->d_ecdf};
+}
+int upload_top_level(rtg_scene* s, const SceneArrays& A) {
+    int rc;
+    if ((rc = upload(s->d_tops, A.tops)) || (rc = upload(s->d_tsph, A.tsph)) ||
+        (rc = upload(s->d_tlas, A.tlas_nodes)) || (rc = upload(s->d_tlasidx, A.tlas_idx)) ||
+        (rc = upload(s->d_gtris, A.gtris)) || (rc = upload(s->d_gents, A.gents)) || (rc = upload(s->d_gtop, A.gtop)) ||
+        (rc = upload(s->d_materials, A.mats)) || (rc = upload(s->d_lights, A.lights)) ||
+        (rc = upload(s->d_topemit, A.top_emit)) || (rc = upload(s->d_etris, A.etris)) || (rc = upload(s->d_ecdf, A.ecdf)))
+        return rc;
+    return RTG_OK;
+}
+
+// rtg_scene_top_hash: 64-bit FNV-1a over the host images of what the top-level phases produce, as uploaded.
+// Order: tops, tsph, TLAS nodes, TLAS indices, gtris, gents, gtop, materials, lights (the object lights
+// included), top_emit, etris, ecdf -- each array as its element count (u64) followed by its bytes -- then the
+// scalars derive_view sets, in the order below (device pointers excluded).  Every hashed record is made of
+// 4-byte fields and filled whole (no padding bytes).
+struct Fnv1a {
+    uint64_t h = 14695981039346656037ull;
+    void bytes(const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; }
+    }
+    template <class T> void value(const T& v) { bytes(&v, sizeof v); }
+    template <class V> void array(const V& v) {
+        value((uint64_t)v.size());
+        if (!v.empty()) bytes(v.data(), v.size() * sizeof(typename V::value_type));
+    }
+};
+uint64_t top_level_hash(const SceneArrays& A, const SceneView& sv) {
+    Fnv1a f;
+    f.array(A.tops); f.array(A.tsph); f.array(A.tlas_nodes); f.array(A.tlas_idx);
+    f.array(A.gtris); f.array(A.gents); f.array(A.gtop);
+    f.array(A.mats); f.array(A.lights); f.array(A.top_emit); f.array(A.etris); f.array(A.ecdf);
+    const int ints[] = {sv.num_tops, sv.num_objects, sv.num_texcoords, sv.num_materials, sv.num_textures, sv.num_lights,
+                        sv.num_emit, sv.tlas_root, sv.num_gtris, sv.num_gents, sv.pt_flags, sv.child_split, sv.absorb_skip,
+                        sv.max_depth, sv.bg_texture, sv.env_light, sv.full, sv.brdf_only, sv.brdf_ts, sv.tex, sv.spot,
+                        sv.heavy, sv.meta_free, sv.has_blur, sv.bary, sv.uni_walk, sv.lean_shadow, sv.lit_nodes, sv.pnt_all};
+    f.value(ints);
+    f.value(sv.tlas_k); f.value(sv.shadow_eps); f.value(sv.int_eps); f.value(sv.background); f.value(sv.ambient);
+    return f.h;
+}
+
+// The frozen part of a descriptor (FrozenDesc), and the first field in which `d` differs from it.
+void freeze_desc(const rtg_scene_desc* d, FrozenDesc& f) {
+    f.num_vertices = d->num_vertices; f.num_texcoords = d->num_texcoords; f.num_faces = d->num_faces;
+    f.num_materials = d->num_materials;
+    f.intersection_test_eps = d->intersection_test_eps;
+    f.objects.assign(d->objects, d->objects + d->num_objects);
+    f.instances.assign(d->instances, d->instances + d->num_instances);
+    f.textures.assign(d->textures, d->textures + d->num_textures);
+    for (rtg_texture_desc& t : f.textures) t.texels = nullptr;
+}
+int check_frozen(const rtg_scene_desc* d, const FrozenDesc& f) {
+    auto changed = [](const std::string& what) {
+        return fail(RTG_ERR_UNSUPPORTED, "rtg_scene_update: " + what + " differs from the build's (frozen: rebuild the scene)");
+    };
+    auto same = [](const auto& a, const auto& b) { return memcmp(&a, &b, sizeof a) == 0; };   // floats by their bits
+    if (d->num_objects != (int)f.objects.size()) return changed("num_objects");
+    if (d->num_instances != (int)f.instances.size()) return changed("num_instances");
+    if (d->num_textures != (int)f.textures.size()) return changed("num_textures");
+    if (d->num_materials != f.num_materials) return changed("num_materials");
+    if (d->num_vertices != f.num_vertices) return changed("num_vertices");
+    if (d->num_texcoords != f.num_texcoords) return changed("num_texcoords");
+    if (d->num_faces != f.num_faces) return changed("num_faces");
+    if (!same(d->intersection_test_eps, f.intersection_test_eps)) return changed("intersection_test_eps");
+    for (int i = 0; i < d->num_objects; i++) {
+        const rtg_object_desc &a = d->objects[i], &b = f.objects[i];
+        const std::string at = "object " + std::to_string(i) + ": ";
+        if (a.type != b.type) return changed(at + "type");
+        if (a.id != b.id) return changed(at + "id");
+        if (a.center != b.center) return changed(at + "center");
+        if (!same(a.radius, b.radius)) return changed(at + "radius");
+        if (!same(a.v, b.v)) return changed(at + "v");
+        if (a.face_first != b.face_first) return changed(at + "face_first");
+        if (a.face_count != b.face_count) return changed(at + "face_count");
+        if (a.smooth != b.smooth) return changed(at + "smooth");
+        if (a.num_textures != b.num_textures) return changed(at + "num_textures");
+        if (!same(a.textures, b.textures)) return changed(at + "textures");
+        if (a.texture_offset != b.texture_offset) return changed(at + "texture_offset");
+        if (a.is_light != b.is_light) return changed(at + "is_light");
+        if (!same(a.radiance, b.radiance)) return changed(at + "radiance");
+    }
+    for (int i = 0; i < d->num_instances; i++) {
+        const rtg_instance_desc &a = d->instances[i], &b = f.instances[i];
+        const std::string at = "instance " + std::to_string(i) + ": ";
+        if (a.base_object != b.base_object) return changed(at + "base_object");
+        if (a.id != b.id) return changed(at + "id");
+    }
+    for (int i = 0; i < d->num_textures; i++) {
+        const rtg_texture_desc &a = d->textures[i], &b = f.textures[i];
+        const std::string at = "texture " + std::to_string(i) + ": ";
+        if (a.kind != b.kind) return changed(at + "kind");
+        if (a.decal != b.decal) return changed(at + "decal");
+        if (a.interp != b.interp) return changed(at + "interp");
+        if (a.noise_conv != b.noise_conv) return changed(at + "noise_conv");
+        if (a.normalizer != b.normalizer) return changed(at + "normalizer");
+        if (!same(a.noise_scale, b.noise_scale)) return changed(at + "noise_scale");
+        if (!same(a.bump_factor, b.bump_factor)) return changed(at + "bump_factor");
+        if (a.width != b.width) return changed(at + "width");
+        if (a.height != b.height) return changed(at + "height");
+    }
+    return RTG_OK;
+}
+
+// The top-level phases: everything from the entries on is a function of the transforms, materials, lights
+// and scalars over per-object results (A.geoms, A.geom_finite, A.small, A.emit, s->bvh, the records) that do
+// not depend on them.  build_scene calls these same functions in this order.
+int top_level_phases(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
+    int rc;
+    top_level_entries(s, d, A);
+    if ((rc = entry_world_bounds(s, A, A.top_model, A.geoms, A.tops))) return rc;
+    top_level_bvh(s, A);
+    flat_group(s, A);
+    shading_tables(d, A, false);
+    return object_lights(s, d, A);
+}
+
+// The kept inputs move between the scene and a SceneArrays (a build's end; around an update's phases).
+void swap_kept(rtg_scene* s, SceneArrays& A) {
+    A.geoms.swap(s->up.geoms);
+    A.geom_finite.swap(s->up.geom_finite);
+    std::swap(A.small, s->up.small);
+    A.emit.swap(s->up.emit);
+}
+
+void finish_build(rtg_scene* s, const rtg_scene_desc* d, SceneArrays& A) {
+    derive_view(s->sv, d, s);
+    s->up.top_hash = top_level_hash(A, s->sv);
+    freeze_desc(d, s->up.frozen);
+    if (s->device < 0) s->up.all_tris.assign(A.tris.begin(), A.tris.end());
+    swap_kept(s, A);
+}
+
+}  // namespace
+
+// The scene can serve a device call: not lost by a failed update, and not host-only (`host_only`: that refusal's text).
+static int scene_ready(const rtg_scene* s, const char* host_only) {
+    if (s->up.broken) return fail(RTG_ERR_INVALID, "scene lost by a failed rtg_scene_update: destroy it");
+    if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, host_only);
+    return RTG_OK;
+}
+
 // ------------------------------------------------------------------ hooks for rtg_multi.cpp
 namespace rtg {
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
 int scene_device(const rtg_scene* s) { return s->device; }
 int scene_render(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* o, float* out_dev, hipStream_t st) {
+    if (s->up.broken) return fail(RTG_ERR_INVALID, "scene lost by a failed rtg_scene_update: destroy it");
     return render_impl(s, cam, o, out_dev, st);
 }
 rtg_render_stats scene_stats(const rtg_scene* s) { return s->stats; }
@@ -3411,7 +3623,7 @@ int32_t rtg_render_device(rtg_scene* s, const rtg_camera_desc* cam, const rtg_re
                           void* stream) {
     return guarded([&]() -> int32_t {
         if (!s || !cam || !rgb_out_device) return fail(RTG_ERR_INVALID, "null argument");
-        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+        if (const int nr = scene_ready(s, "host-only scene cannot render")) return nr;
         HIP_TRY(hipSetDevice(s->device));
         if (opts && (opts->num_devices > 1 || opts->devices)) return render_multi(s, cam, opts, rgb_out_device, (hipStream_t)stream);
         return render_impl(s, cam, opts, rgb_out_device, (hipStream_t)stream);
@@ -3441,7 +3653,7 @@ int32_t rtg_render(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_op
     return guarded([&]() -> int32_t {
         if (!s || !cam || !rgb_out) return fail(RTG_ERR_INVALID, "null argument");
         if (cam->nx < 1 || cam->ny < 1) return fail(RTG_ERR_INVALID, "bad camera");
-        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+        if (const int nr = scene_ready(s, "host-only scene cannot render")) return nr;
         HIP_TRY(hipSetDevice(s->device));
         const int out_rows = opts && opts->compact_rows ? rtg_shard_rows(cam->ny, opts->row_offset, opts->row_stride,
                                                                          opts->row_block) : cam->ny;
@@ -3555,7 +3767,7 @@ int32_t rtg_frame_create(rtg_scene* s, const rtg_camera_desc* cam, const rtg_ren
     return guarded([&]() -> int32_t {
         if (out) *out = nullptr;
         if (!s || !cam || !out) return fail(RTG_ERR_INVALID, "null argument");
-        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+        if (const int nr = scene_ready(s, "host-only scene cannot render")) return nr;
         if (cam->nx < 1 || cam->ny < 1 || cam->num_samples < 1) return fail(RTG_ERR_INVALID, "bad camera");
         if (cam->integrator != RTG_INTEGRATOR_REFERENCE && cam->integrator != RTG_INTEGRATOR_PATH)
             return fail(RTG_ERR_INVALID, "unknown integrator");
@@ -3615,6 +3827,70 @@ int32_t rtg_frame_destroy(rtg_frame* f) {
         if (it != g_frame_scenes.end()) g_frame_scenes.erase(it);
     }
     delete f;
+    return RTG_OK;
+}
+
+// rtg_scene_update: the top level of a built scene again, from the descriptor's free part.
+int32_t rtg_scene_update(rtg_scene* s, const rtg_scene_desc* d) {
+    return guarded([&]() -> int32_t {
+        if (!s || !d) return fail(RTG_ERR_INVALID, "null argument");
+        if (s->replica) return fail(RTG_ERR_INVALID, "a scene replica cannot be updated");
+        if (s->up.broken) return fail(RTG_ERR_INVALID, "scene lost by a failed rtg_scene_update: destroy it");
+        {
+            std::lock_guard<std::mutex> lk(g_frames_mu);
+            if (std::count(g_frame_scenes.begin(), g_frame_scenes.end(), s) > 0)
+                return fail(RTG_ERR_INVALID, "scene has live frames: destroy them first");
+        }
+        PhaseClock whole;
+        int rc;
+        if ((rc = validate(d, true)) || (rc = check_frozen(d, s->up.frozen))) return rc;
+        if (d->num_lights + (int)s->up.emit.size() > kMaxLights)
+            return fail(RTG_ERR_UNSUPPORTED, "more than 64 lights + object lights");
+        if (s->device >= 0) HIP_TRY(hipSetDevice(s->device));
+
+        // From here on the scene changes: a failure, or an exception, leaves it for rtg_scene_destroy only.
+        struct Kept {                    // the kept inputs go back to the scene on every path
+            rtg_scene* s;
+            SceneArrays& A;
+            bool done = false;
+            ~Kept() { swap_kept(s, A); if (!done) s->up.broken = true; }
+        };
+        auto lost = [](int code) {
+            return fail(code, std::string(rtg_last_error()) + " (rtg_scene_update failed midway: the scene is unusable, destroy it)");
+        };
+        PhaseClock pc;
+        SceneArrays A;
+        swap_kept(s, A);
+        Kept kept{s, A};
+        compose_matrices(s, d, A);
+        if ((rc = top_level_phases(s, d, A))) return lost(rc);
+        const double top_ms = pc.lap("update top_level");
+        double upload_ms = 0.0;
+        uint64_t upload_bytes = 0;
+        if (s->device >= 0) {
+            if ((rc = upload_top_level(s, A))) return lost(rc);
+            for (const DBuf* b : top_level_buffers(s)) upload_bytes += b->used;
+            // (the fan-out's replicas are copies of the old buffers: the next num_devices render makes new ones)
+            multi_free(s->multi);
+            s->multi = nullptr;
+            upload_ms = pc.lap("update upload");
+        }
+        derive_view(s->sv, d, s);
+        s->up.top_hash = top_level_hash(A, s->sv);
+        kept.done = true;
+        rtg_build_stats& bs = s->bst;    // (tlas_nodes and flat_group_entries: the phases set them)
+        bs.top_level_ms = top_ms;
+        bs.upload_ms = upload_ms;
+        bs.upload_bytes = upload_bytes;
+        bs.total_ms = whole.lap();
+        return RTG_OK;
+    });
+}
+
+int32_t rtg_scene_top_hash(const rtg_scene* s, uint64_t* out) {
+    if (!s || !out) return fail(RTG_ERR_INVALID, "null argument");
+    if (s->replica) return fail(RTG_ERR_INVALID, "a scene replica has no host images");
+    *out = s->up.top_hash;
     return RTG_OK;
 }
 
@@ -4031,7 +4307,7 @@ int32_t rtg_trace_closest(rtg_scene* s, const rtg_ray* rays, int32_t n, rtg_hit*
     return guarded([&]() -> int32_t {
         if (!s || n < 0 || (n && (!rays || !hits))) return fail(RTG_ERR_INVALID, "bad arguments");
         if (n == 0) return RTG_OK;
-        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot trace");
+        if (const int nr = scene_ready(s, "host-only scene cannot trace")) return nr;
         HIP_TRY(hipSetDevice(s->device));
         // the rays as RayQ planes (with times: API rays may carry any time)
         std::vector<float> rr((size_t)7 * n);
@@ -4080,7 +4356,7 @@ static int query_args(const rtg_scene* s, int32_t n, bool arrays, bool* done) {
     *done = false;
     if (!s || n < 0 || (n && !arrays)) return fail(RTG_ERR_INVALID, "bad arguments");
     if (n == 0) { *done = true; return RTG_OK; }
-    if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot trace");
+    if (const int nr = scene_ready(s, "host-only scene cannot trace")) return nr;
     return RTG_OK;
 }
 static int query_finish(hipStream_t st, const char* what) {
@@ -4238,7 +4514,7 @@ static int aov_device(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render
     PassDevA ps{};
     if ((rc = pixel_order(o, cam, ps))) return rc;
     ps.s0 = ao.first_sample; ps.ns = window;
-    if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot render");
+    if (const int nr = scene_ready(s, "host-only scene cannot render")) return nr;
     HIP_TRY(hipSetDevice(s->device));
     const int rows_owned = ps.rows_owned, npix = rows_owned * cam->nx;
     const int out_rows = o.compact_rows ? rows_owned : cam->ny;
@@ -4329,7 +4605,7 @@ int32_t rtg_camera_rays(rtg_scene* s, const rtg_camera_desc* cam, uint64_t seed,
         int window = 0, rc;
         if ((rc = aov_window(cam, first_sample, sample_count, window))) return rc;
         if ((long long)cam->nx * cam->ny > (1LL << 30)) return fail(RTG_ERR_UNSUPPORTED, "image too large");
-        if (s->device < 0) return fail(RTG_ERR_NO_DEVICE, "host-only scene cannot form rays");
+        if (const int nr = scene_ready(s, "host-only scene cannot form rays")) return nr;
         HIP_TRY(hipSetDevice(s->device));
         const int npix = cam->nx * cam->ny;
         // a row-major pass: one-row tiles in one-tile bands over every row make tile order image order

@@ -430,6 +430,81 @@ struct PtRad {
 };
 constexpr size_t kCarryBytes = 16;    // float4 per queued ray
 
+// The bounding-sphere radius of a transformed mesh entry (TopObject::bs[3]; entry_bounding_sphere, rtg_host.cpp):
+// the largest squared distance from the centre c0 of any triangle corner taken through the model matrix, in
+// double.  One function for the host pass (scene builds) and the kernel (rtg_radius.hip, rtg_scene_update), so
+// both evaluate the same expressions in the same order: corner 0 is p0.xyz, corners 1 and 2 are p0 - e1 and
+// p0 - e2; per corner the three row sums M v + M[3] - c0, left to right, and their squares added in order.
+// Host and device are built with -ffp-contract=off, double add and multiply are IEEE on both, and the
+// "NaN wins" maximum does not depend on the order of its operands (every value is a sum of squares: no -0;
+// any NaN result means "no sphere"), so the two sides agree bit for bit.
+struct RadiusXf {
+    double m[4][3];     // the model matrix's columns (glm m[col][row], rows 0-2), widened from float
+    double c0[3];
+};
+__host__ __device__ inline double radius2_fold(double mx2, double v) { return v > mx2 || v != v ? v : mx2; }
+__host__ __device__ inline double tri_radius2(const TriGeom& tg, const RadiusXf& X, double mx2) {
+    const double a[3] = {tg.p0.x, tg.p0.y, tg.p0.z};
+    const double e[2][3] = {{tg.p0.w, tg.p1.x, tg.p1.y}, {tg.p1.z, tg.p1.w, tg.p2.x}};
+    for (int q = 0; q < 3; q++) {
+        double v[3], d2 = 0.0;
+        for (int z = 0; z < 3; z++) v[z] = q == 0 ? a[z] : a[z] - e[q - 1][z];
+        for (int r = 0; r < 3; r++) {
+            const double w = X.m[0][r] * v[0] + X.m[1][r] * v[1] + X.m[2][r] * v[2] + X.m[3][r] - X.c0[r];
+            d2 += w * w;
+        }
+        mx2 = radius2_fold(mx2, d2);    // NaN propagates (no sphere)
+    }
+    return mx2;
+}
+// The kernel's launcher: tris = n records on the device (n >= 1), part = kRadiusPartials doubles of device
+// workspace; *r2 = the maximum (synchronous).  ms (may be null): the two launches' device time from HIP events.
+constexpr int kRadiusBlock = 256;
+constexpr int kRadiusMaxBlocks = 1024;
+constexpr int kRadiusPartials = kRadiusMaxBlocks + 1;
+int entry_radius2_device(const TriGeom* tris, int n, const RadiusXf& X, double* part, double* r2, float* ms,
+                         std::string& err);
+
+// What a built scene keeps for rtg_scene_update: the inputs of the top-level phases that do not
+// depend on the free part of the descriptor, and the update's own state.  The build fills the kept inputs in its
+// SceneArrays (rtg_host.cpp) and hands them over at its end; an update takes them back for the phases.
+//
+// The reference-order records of the meshes that may join the flat group (<= kFlatMaxPrims triangles), with each
+// position's leaf (tie order) and gate flag: object i's nprims rows start at first[i] (-1: none kept).
+struct SmallMeshes {
+    std::vector<int> first;
+    std::vector<TriGeom> tris;
+    std::vector<int> pos_leaf;     // the first position of the record's reference leaf (scene-wide) ...
+    std::vector<char> pos_gated;   // ... and whether that leaf's parent (gates[]) is not the root
+};
+// An is_light object's object-space corners in parse order, xyz each (object_lights): a sphere's centre, else
+// three per triangle.
+struct EmitSource {
+    int object;
+    std::vector<float> corners;
+};
+// The frozen part of the descriptor a scene was built from: rtg_scene_update refuses a descriptor that differs
+// in it.  Pointers are not kept (texels is null in `textures`).
+struct FrozenDesc {
+    int num_vertices = 0, num_texcoords = 0, num_faces = 0, num_materials = 0;
+    float intersection_test_eps = 0.0f;
+    std::vector<rtg_object_desc> objects;
+    std::vector<rtg_instance_desc> instances;
+    std::vector<rtg_texture_desc> textures;
+};
+struct SceneUpdate {
+    std::vector<Geometry> geoms;
+    std::vector<char> geom_finite;   // per object: every primitive box coordinate finite
+    SmallMeshes small;
+    std::vector<EmitSource> emit;
+    std::vector<TriGeom> all_tris;   // a host-only scene: every reference-order record (a device scene's are in d_tris)
+    FrozenDesc frozen;
+    double* d_radius = nullptr;      // device: the radius kernel's partials (kRadiusPartials), from the first update on
+    uint64_t top_hash = 0;           // rtg_scene_top_hash: of the last build or update
+    bool broken = false;             // an update failed after its device work began: destroy only
+};
+
+
 // Host-side launchers (rtg_device.hip) ------------------------------------------------
 // Where a render's samples go.  rtg_render*: the scene's accumulator, the camera's whole sample range,
 // nothing accumulated before, no moments (target == nullptr).  A frame (rtg_frame_add_samples): its own

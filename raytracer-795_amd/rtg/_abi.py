@@ -281,6 +281,9 @@ EXPORTS = {
     "rtg_trace_closest_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "rtg_trace_occluded_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                               C.c_void_p]),
+    # ABI 10 additions: updating a built scene in place
+    "rtg_scene_update": (C.c_int32, [C.c_void_p, C.POINTER(SceneDesc)]),
+    "rtg_scene_top_hash": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -660,6 +660,28 @@ def _renderer_occluded_device(self, rays_ptr: int, n: int, out_ptr: int, tmax_pt
                                                C.c_void_p(stream)), self.lib)
 
 
+# ---------------------------------------------------------------------------- scene updates
+def _renderer_update(self, scene: Scene):
+    """Move the resident scene to `scene` in place (rtg_scene_update): transforms, blur vectors, material
+    assignments and tables, lights and the scene scalars may differ from the scene this Renderer was built
+    from; geometry, textures, object counts and intersection_test_eps may not (RtgError, RTG_ERR_UNSUPPORTED,
+    naming the field).  Only the top level is rebuilt and uploaded: every later call gives the bits of a fresh
+    Renderer(scene).  Frames of this Renderer must be closed first."""
+    desc, keep = scene.to_desc(geometry=False)
+    A.check(self.lib.rtg_scene_update(self.handle, C.byref(desc)), self.lib)
+    self.scene = scene
+    self._keep = keep
+
+
+def _renderer_top_hash(self) -> int:
+    """rtg_scene_top_hash: a 64-bit fingerprint of the scene's top level as built or last updated."""
+    h = C.c_uint64()
+    A.check(self.lib.rtg_scene_top_hash(self.handle, C.byref(h)), self.lib)
+    return int(h.value)
+
+
+Renderer.update = _renderer_update
+Renderer.top_hash = _renderer_top_hash
 Renderer.occluded = _renderer_occluded
 Renderer.trace_device = _renderer_trace_device
 Renderer.occluded_device = _renderer_occluded_device

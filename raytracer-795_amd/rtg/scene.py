@@ -181,14 +181,14 @@ class Scene:
     environment_light: int = -1
 
     # ------------------------------------------------------------------ C ABI
-    def to_desc(self):
-        """Return (SceneDesc, keepalive) — the descriptor of include/rtg.h."""
+    def to_desc(self, geometry: bool = True):
+        """Return (SceneDesc, keepalive) — the descriptor of include/rtg.h (geometry=False: frozen arrays NULL, rtg_scene_update)."""
         keep = []
 
-        def arr(a, dtype, ctype):
-            a = np.ascontiguousarray(a, dtype=dtype)
+        def arr(a, dtype, ctype, frozen=False):
+            a = a if frozen and not geometry else np.ascontiguousarray(a, dtype=dtype)
             keep.append(a)
-            if a.size == 0:
+            if a.size == 0 or (frozen and not geometry):
                 return C.cast(None, C.POINTER(ctype)), a
             return a.ctypes.data_as(C.POINTER(ctype)), a
 
@@ -201,9 +201,9 @@ class Scene:
         d.ambient_light = A.F3(*map(float, np.asarray(self.ambient, f32)))
         d.background_texture = int(self.background_texture)
         d.environment_light = int(self.environment_light)
-        d.vertices, v = arr(np.asarray(self.vertices, f32).reshape(-1, 3), f32, C.c_float)
+        d.vertices, v = arr(np.asarray(self.vertices, f32).reshape(-1, 3), f32, C.c_float, True)
         d.num_vertices = v.shape[0]
-        d.texcoords, t = arr(np.asarray(self.texcoords, f32).reshape(-1, 2), f32, C.c_float)
+        d.texcoords, t = arr(np.asarray(self.texcoords, f32).reshape(-1, 2), f32, C.c_float, True)
         d.num_texcoords = t.shape[0]
         faces, face_first = [], []
         n = 0
@@ -215,8 +215,8 @@ class Scene:
                 n += fa.shape[0]
             else:
                 face_first.append(0)
-        allf = np.concatenate(faces) if faces else np.zeros((0, 3), np.int32)
-        d.faces, fa = arr(allf, np.int32, C.c_int32)
+        allf = np.concatenate(faces) if faces and geometry else np.broadcast_to(np.int32(0), (n, 3))   # (shape only)
+        d.faces, fa = arr(allf, np.int32, C.c_int32, True)
         d.num_faces = fa.shape[0]
         d.translations, a = arr(np.asarray(self.translations, f32).reshape(-1, 3), f32, C.c_float)
         d.num_translations = a.shape[0]
@@ -289,7 +289,7 @@ class Scene:
                 tex = np.ascontiguousarray(tx.texels, f32)
                 keep.append(tex)
                 td.height, td.width = tex.shape[0], tex.shape[1]
-                td.texels = tex.ctypes.data_as(A.PF)
+                td.texels = tex.ctypes.data_as(A.PF) if geometry else None
         keep.append(texs)
         lts = (A.LightDesc * max(1, len(self.lights)))()
         for i, l in enumerate(self.lights):
