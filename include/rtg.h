@@ -800,6 +800,51 @@ int32_t rtg_scene_update(rtg_scene* scene, const rtg_scene_desc* desc);
    hashes: an updated scene can be held against a fresh one without rendering. */
 int32_t rtg_scene_top_hash(const rtg_scene* scene, uint64_t* out);
 
+/* ---- ABI 10 additions: rendering caller-supplied primary rays -------------------
+   Additive: the version stays 10, no struct grows.
+
+   rtg_render_rays runs the integrator -- the reference's or the path tracer -- over primary rays the
+   caller supplies: panoramas, fisheye and orthographic views, cube-map and probe captures, lightmap
+   texels, any camera model.  rays[((size_t)y * nx + x) * num_samples + s] is sample s of pixel (x, y):
+   rtg_camera_rays' layout with first_sample = 0.  Everything else is rtg_render's for a camera of the
+   same nx, ny, num_samples, integrator and pt_flags: ray (pixel, s) takes the place of primary ray
+   (pixel, s); every random draw below level 0 is keyed by pixel = y * nx + x and sample s under
+   opts->seed; a miss takes the background of pixel (x, y), with the background texture's (row, col) rule
+   and its transposition for num_samples == 1; a pixel's samples are summed in index order and divided as
+   rtg_render divides; the output layout, the row shards (row_offset, row_stride, row_block, compact_rows),
+   traversal, schedule, max_batch_rays, streams, tile_band, the segment options, collect_stats and
+   collect_timing mean what they mean there.  So rendering a camera's own rays (rtg_camera_rays under the
+   same seed) gives rtg_render's image bit for bit.  Directions are used as given, not normalised: supply
+   unit directions (the reference's own rays are unit).
+
+   rtg_last_render_stats then reports primary_rays = owned pixels x num_samples, the other fields as after
+   rtg_render.  The call may interleave with renders, frames, feature buffers and queries on the scene
+   (never run concurrently with them) and leaves a live frame untouched.  The _device form reads the
+   caller's array on the scene's device in place and copies nothing; it is enqueued on `stream`
+   (hipStream_t) and synchronous on return.  The host form stages the rays (28 B per ray) and the frame in
+   device memory for the call and releases them.
+
+   Checked in this order, all before anything is traced: a NULL scene, image, rays or output
+   (RTG_ERR_INVALID); nx, ny or num_samples < 1, a non-zero pad, an unknown integrator or pt_flags bit
+   (RTG_ERR_INVALID); the options, as rtg_render reports them; num_devices > 1 or devices != NULL
+   (RTG_ERR_UNSUPPORTED: the rays live on one device); a host-only scene (RTG_ERR_NO_DEVICE); then, on the
+   device, the rays the call will read (a shard: its owned rows only): a ray with a non-finite origin,
+   direction or time, or with the direction (+-0, +-0, +-0), gives RTG_ERR_INVALID, the message naming the
+   lowest such index, and the output is not written.
+
+   Not offered: frames or feature buffers over caller rays, a CLI / XML surface, multi-device fan-out. */
+typedef struct rtg_ray_image {   /* 32 bytes */
+    int32_t nx, ny;              /* image the rays are laid over */
+    int32_t num_samples;         /* rays per pixel, >= 1 (need not be a square) */
+    int32_t integrator;          /* rtg_integrator */
+    int32_t pt_flags;            /* rtg_pt_flags */
+    int32_t pad[3];              /* must be 0 */
+} rtg_ray_image;
+int32_t rtg_render_rays(rtg_scene* scene, const rtg_ray_image* image, const rtg_ray* rays,
+                        const rtg_render_opts* opts, float* rgb_out);
+int32_t rtg_render_rays_device(rtg_scene* scene, const rtg_ray_image* image, const rtg_ray* rays_device,
+                               const rtg_render_opts* opts, float* rgb_out_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1843,7 +1843,7 @@ __global__ void __launch_bounds__(kTraceBlock) RTG_TRACE_ATTR k_trace(const Scen
             tmax = FLT_MAX;
         }
         // a wave of camera samples only (a pixel's samples, or adjacent pixels'): the wave-uniform walk
-        constexpr bool KUNI = GEN && !TLAS && !EXHAUSTIVE;
+        constexpr bool KUNI = GEN && !TLAS && !EXHAUSTIVE && !kRayPass<PS>;   // (caller-supplied rays need not be alike: a ray pass takes the per-lane walk -- the same bits)
         const bool uni = KUNI && sv.uni_walk && (int)(blockIdx.x * blockDim.x) >= nq;
         HitRec h = closest_hit<EXHAUSTIVE, STATS, TLAS, KUNI>(sv, o, d, time, tmax, s_stack + threadIdx.x, kTraceBlock, st,
                                                              s_tstack + (TLAS ? threadIdx.x : 0), uni,
@@ -3247,16 +3247,44 @@ __global__ void __launch_bounds__(kOccludedBlock) RTG_OCCLUDED_ATTR k_occluded(c
     out[i] = occ ? 1 : 0;
 }
 
+// primary_ray of a ray pass (rtg_render_rays; here, behind the kernels, so that their lines stay
+// where they are: the templates find it at their instantiation, by the pass type's namespace): the caller's ray of the slot's (pixel, sample), read in
+// place -- seven dword loads of a 28-byte record, adjacent lanes on adjacent records (a pixel's samples, then
+// the next pixel of the tile row).  The direction is used as given.
+DEV void primary_ray(const CameraDev& cam, const PassDevR& ps, uint64_t, int i, f3& o_out, f3& d_out, float& time_out) {
+    uint32_t pixel, sample;
+    int x, y;
+    slot_pixel(cam, ps, i, pixel, sample, x, y);
+    const float* __restrict__ r = reinterpret_cast<const float*>(ps.rays) + ((size_t)pixel * (size_t)ps.nsamp + sample) * 7;
+    o_out = mk(r[0], r[1], r[2]);
+    d_out = mk(r[3], r[4], r[5]);
+    time_out = r[6];
+}
+
 // ------------------------------------------------------------------ launchers
 static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 
 // The launchers that hand a pass to the kernels are templates over the pass type: PassDev (rtg_render, plain
-// frames), or PassDevA (an adaptive frame), which falls back to PassDev when it is plain().
+// frames), PassDevA (an adaptive frame), which falls back to PassDev when it is plain(), or
+// PassDevR (caller-supplied primary rays, §25).
 // with_pass makes that choice, for every launcher: f(pass) runs with the type whose kernels the pass takes.
+// A ray pass (PassArg::rays set) takes PassDevR where the launch generates level 0 (gen) and is a
+// PassDev everywhere else: its slot -> pixel map is a PassDev's, so queued-only launches and the accumulation
+// run the PassDev kernels.  with_pass never hands out a PassDevR (the accumulation: no instantiation for it);
+// with_gen_pass does, for the launchers of the kernels that can generate primary rays.
 template <class F>
-static void with_pass(const PassDevA& ps, F&& f) {
-    if (ps.plain()) f(static_cast<const PassDev&>(ps));
-    else f(ps);
+static void with_pass(const PassArg& ps, F&& f) {
+    if (ps.rays || ps.plain()) f(static_cast<const PassDev&>(ps));
+    else f(static_cast<const PassDevA&>(ps));
+}
+template <class F>
+static void with_gen_pass(const PassArg& ps, bool gen, F&& f) {
+    if (ps.rays && gen) {
+        PassDevR r;
+        static_cast<PassDev&>(r) = ps;
+        r.rays = ps.rays; r.nsamp = ps.nsamp;
+        f(r);
+    } else with_pass(ps, f);
 }
 // gen_cam non-null: the launch generates primary rays (either integrator), else the pass is not read
 template <class PS>
@@ -3288,12 +3316,12 @@ static void launch_trace_t(const SceneView& sv, const RayQ rays, HitRec* hits, i
 void launch_trace_queued(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, hipStream_t st) {
     launch_trace_t(sv, rays, hits, n, exhaustive, nullptr, st, nullptr, PassDev{}, 0, /*compact=*/false, 0, 0);
 }
-void launch_trace(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+void launch_trace(const SceneView& sv, const CameraDev& cam, const PassArg& ps, uint64_t seed, const StepIO& io,
                   int exhaustive, Counters* ctr, hipStream_t st) {
     if (!io.gen)
         launch_trace_t(sv, io.rays, io.hits, io.n, exhaustive, ctr, st, nullptr, PassDev{}, seed, /*compact=*/true, io.nq, io.gbase);
     else
-        with_pass(ps, [&](const auto& p) {
+        with_gen_pass(ps, true, [&](const auto& p) {
             launch_trace_t(sv, io.rays, io.hits, io.n, exhaustive, ctr, st, &cam, p, seed, /*compact=*/true, io.nq, io.gbase);
         });
 }
@@ -3325,7 +3353,7 @@ static void launch_shade_t(const SceneView& sv, const CameraDev& cam, const PS& 
         if (io.gen)                                                                                               \
             hipLaunchKernelGGL((k_shade<F, S, B, T, true, PS>), gr, bl, 0, st, sv, cam, io.level, ps, seed, io.rays, io.meta, io.hits, np, sp, \
                                io.slist, io.next_rays, io.next_meta, io.qcount, n, io.nq, io.gbase, io.lv_in, io.lv_out); \
-        else                                                                                                      \
+        else if constexpr (!kRayPass<PS>)   /* (a ray pass comes here only with gen: with_pass) */               \
             hipLaunchKernelGGL((k_shade<F, S, B, T, false, PS>), gr, bl, 0, st, sv, cam, io.level, ps, seed, io.rays, io.meta, io.hits, np, sp, \
                                io.slist, io.next_rays, io.next_meta, io.qcount, n, io.nq, io.gbase, io.lv_in, io.lv_out); \
     } while (0)
@@ -3339,9 +3367,9 @@ static void launch_shade_t(const SceneView& sv, const CameraDev& cam, const PS& 
     else RTG_SHADE(false, false, kShadeBlock, false, g, b);
 #undef RTG_SHADE
 }
-void launch_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+void launch_shade(const SceneView& sv, const CameraDev& cam, const PassArg& ps, uint64_t seed, const StepIO& io,
                   hipStream_t st) {
-    with_pass(ps, [&](const auto& p) { launch_shade_t(sv, cam, p, seed, io, st); });
+    with_gen_pass(ps, io.gen, [&](const auto& p) { launch_shade_t(sv, cam, p, seed, io, st); });
 }
 // One k_shadow launch, its variant by the traversal, the counters and the top-level BVH.  PT: a light's list
 // of the path tracer (launch_pt_shadow), else a level's Whitted list.
@@ -3400,7 +3428,7 @@ static void launch_pt_shade_t(const SceneView& sv, const CameraDev& cam, const P
 #define RTG_PT_LAUNCH(F, S, B)                                                                                    \
     do {                                                                                                          \
         if (io.gen) RTG_PT_LAUNCH1(F, S, B, true);                                                                \
-        else RTG_PT_LAUNCH1(F, S, B, false);                                                                      \
+        else if constexpr (!kRayPass<PS>) RTG_PT_LAUNCH1(F, S, B, false);   /* (as RTG_SHADE) */                  \
     } while (0)
     // textures / area / environment lights need the full variant; BRDFs alone do not
     if (sv.full && !sv.brdf_only) {
@@ -3415,9 +3443,9 @@ static void launch_pt_shade_t(const SceneView& sv, const CameraDev& cam, const P
 #undef RTG_PT_LAUNCH
 #undef RTG_PT_LAUNCH1
 }
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassArg& ps, uint64_t seed, const StepIO& io,
                      Counters* ctr, hipStream_t st) {
-    with_pass(ps, [&](const auto& p) { launch_pt_shade_t(sv, cam, p, seed, io, ctr, st); });
+    with_gen_pass(ps, io.gen, [&](const auto& p) { launch_pt_shade_t(sv, cam, p, seed, io, ctr, st); });
 }
 void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_nodes, const NodeRec* grand_nodes, int n,
                      int n_child, int n_grand, hipStream_t st) {
@@ -3486,11 +3514,11 @@ static void launch_accumulate_t(const SceneView& sv, const NodeRec* level0, cons
     }
 }
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDevA& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
+                              float* acc, const PassArg& ps, int nx, int mode, hipStream_t st, float* mom, int mom_k0) {
     with_pass(ps, [&](const auto& p) { launch_accumulate_planes_t(sv, level0, level1, resolve, acc, p, nx, mode, st, mom, mom_k0); });
 }
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
-                       const PassDevA& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
+                       const PassArg& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
                        const NodeRec* level2, int n2, float* mom, int mom_k0) {
     with_pass(ps, [&](const auto& p) {
         launch_accumulate_t(sv, level0, level1, resolve, acc, p, nx, mode, st, whitted, n0, n1, level2, n2, mom, mom_k0);
@@ -3711,6 +3739,52 @@ void launch_aov_place(const AovPlanes& in, const AovPlanes& out, int nx, int out
 void launch_camera_rays(const CameraDev& cam, const PassDev& ps, uint64_t seed, int n, rtg_ray* out, hipStream_t st) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_camera_rays, dim3(nblk(n, 256)), dim3(256), 0, st, cam, ps, seed, n, out);
+}
+
+// ------------------------------------------------------------------ rtg_render_rays: ray validation
+// One pass over the rays a call will read -- the shard's owned rows, row_len = nx * num_samples records each,
+// contiguous in the caller's array -- before anything is traced.  A ray is bad when one of its seven floats is
+// not finite or its direction is (+-0, +-0, +-0): a NaN direction that misses would reach background()'s
+// environment lookup and index a texture with a converted NaN.  *bad (preset to ~0) receives the lowest bad
+// index of the caller's array: lanes stride over the owned rays, a block reduces its minimum (shuffles, then
+// the four wave results through LDS) and issues at most one atomicMin.
+constexpr int kCheckBlock = 256;
+__global__ void __launch_bounds__(kCheckBlock) k_check_rays(const rtg_ray* __restrict__ rays, unsigned long long n,
+                                                            unsigned long long row_len, int row_offset, int row_stride,
+                                                            int row_block, unsigned long long* __restrict__ bad) {
+    __shared__ unsigned long long s_min[kCheckBlock / 64];
+    unsigned long long lo = ~0ull;
+    const unsigned long long step = (unsigned long long)gridDim.x * kCheckBlock;
+    for (unsigned long long j = (unsigned long long)blockIdx.x * kCheckBlock + threadIdx.x; j < n; j += step) {
+        const unsigned long long k = j / row_len, r = j - k * row_len;
+        const unsigned long long idx = (unsigned long long)shard_row((int)k, row_offset, row_stride, row_block) * row_len + r;
+        const unsigned* w = reinterpret_cast<const unsigned*>(rays) + idx * 7;
+        unsigned v[7];
+        for (int c = 0; c < 7; c++) v[c] = w[c];
+        bool nonfinite = false;
+        for (int c = 0; c < 7; c++) nonfinite |= (v[c] & 0x7F800000u) == 0x7F800000u;
+        const bool zero_dir = ((v[3] | v[4] | v[5]) & 0x7FFFFFFFu) == 0u;
+        if ((nonfinite || zero_dir) && idx < lo) lo = idx;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(lo, off, 64);
+        lo = o < lo ? o : lo;
+    }
+    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = lo;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kCheckBlock / 64; k++) lo = s_min[k] < lo ? s_min[k] : lo;
+        if (lo != ~0ull) atomicMin(bad, lo);
+    }
+}
+void launch_check_rays(const rtg_ray* rays, int rows_owned, int nx, int nsamp, int row_offset, int row_stride, int row_block,
+                       unsigned long long* bad, hipStream_t st) {
+    const unsigned long long row_len = (unsigned long long)nx * (unsigned long long)nsamp;
+    const unsigned long long n = (unsigned long long)rows_owned * row_len;
+    if (n == 0) return;
+    const unsigned long long blocks = std::min<unsigned long long>((n + kCheckBlock - 1) / kCheckBlock, 1ull << 16);
+    hipLaunchKernelGGL(k_check_rays, dim3((unsigned)blocks), dim3(kCheckBlock), 0, st, rays, n, row_len, row_offset, row_stride,
+                       row_block, bad);
 }
 
 }  // namespace rtg

@@ -2728,7 +2728,7 @@ struct Render {
     RenderTarget tg{};
     CameraDev cd{};
     SceneView sv{};                    // per-render view: the path tracer's light loop
-    PassDevA order{};                  // the pixel order and the target's list / sample order: every pass's base
+    PassArg order{};                   // the pixel order and the target's list / sample order (or the caller's rays, §25): every pass's base
     // plan
     int npix = 0, total = 0;           // npix: pixel ordinals (an adaptive frame: its active pixels, §15); total: samples per pixel of this call
     bool pt = false, timing = false, stream = false;
@@ -2744,17 +2744,17 @@ struct Render {
     rtg_render_stats stt{};
     uint64_t shadow_listed = 0;
     std::deque<int> waiting;           // lanes with a step in flight, in enqueue order
-    std::vector<PassDevA> plist;       // pass schedule: the frame's passes
+    std::vector<PassArg> plist;        // pass schedule: the frame's passes
     struct {                           // stream schedule: the frame's slot cursor and the open segment
-        PassDevA F;
+        PassArg F;
         long long cursor = 0, end = 0, slots = 0;
         double node_bytes = 0.0;
         bool closed = false;
     } seg;
 
-    Render(rtg_scene* s_, const rtg_camera_desc* cam_) : s(s_), cam(cam_) {}
+    const rtg_ray* rays = nullptr; Render(rtg_scene* s_, const rtg_camera_desc* cam_, const rtg_ray* rays_ = nullptr) : s(s_), cam(cam_), rays(rays_) {}   // rays: rtg_render_rays (§25), the caller's primary rays (device), else the camera's
     int plan(const rtg_render_opts* opts, const RenderTarget* target);
-    int step(Lane& ln, const PassDevA& ps, const StepIO& io);
+    int step(Lane& ln, const PassArg& ps, const StepIO& io);
     int drain(int& k, unsigned& next);
     int run_passes();
     int level_step(Lane& ln);
@@ -2791,7 +2791,7 @@ int Render::plan(const rtg_render_opts* opts, const RenderTarget* target) {
     tg = target ? *target : RenderTarget{nullptr, nullptr, 0, cam->num_samples, 0};
     total = tg.ns;
     npix = tg.active ? tg.nactive : order.rows_owned * cam->nx;
-    order.active = tg.active; order.ord_m = tg.ord_m; order.ord_n = tg.ord_n;
+    order.active = tg.active; order.ord_m = tg.ord_m; order.ord_n = tg.ord_n; order.rays = rays; order.nsamp = cam->num_samples;
     if (cam->integrator != RTG_INTEGRATOR_REFERENCE && cam->integrator != RTG_INTEGRATOR_PATH)
         return fail(RTG_ERR_INVALID, "unknown integrator");
     if (o.tile_band < 0 || o.segment_pixels < 0 || o.segment_nodes < 0)
@@ -2861,7 +2861,7 @@ int Render::plan(const rtg_render_opts* opts, const RenderTarget* target) {
 
 // Enqueue one step on its lane: trace, shade, the count read-back, the shadow queries -- a level of a pass
 // or a step of the stream schedule; the schedule fills `io` from its own buffers.
-int Render::step(Lane& ln, const PassDevA& ps, const StepIO& io) {
+int Render::step(Lane& ln, const PassArg& ps, const StepIO& io) {
     if (timing) HIP_TRY(hipEventRecord(ln.ev_t[0], ln.st));
     // (primary rays are generated inside k_trace / k_shade / k_pt_shade: there is no level-0 ray buffer)
     launch_trace(sv, cd, ps, o.seed, io, exhaustive, sctr, ln.st);
@@ -2957,13 +2957,13 @@ int Render::level_step(Lane& ln) {
     if (pt)
         io.pr = PtRad{Lc.carry.as<float4>(), Ln.carry.as<float4>(), ln.prad.as<float4>(),
                       ln.lcnt.as<unsigned>() + (size_t)level * std::max(nL, 1)};
-    io.uni_from = level < kUniShadowLevels ? 0 : INT_MAX;
+    io.uni_from = level < kUniShadowLevels && !rays ? 0 : INT_MAX;    // (caller rays: the per-lane walk)
     return step(ln, plist[ln.pass], io);
 }
 
 int Render::start_pass(Lane& ln) {
     ln.pass = ln.passes[ln.next_pass++];
-    const PassDevA& ps = plist[ln.pass];
+    const PassArg& ps = plist[ln.pass];
     const int n0 = ps.ns * ps.npass;
     int rc;
     if ((rc = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc;
@@ -2981,7 +2981,7 @@ int Render::start_pass(Lane& ln) {
 }
 
 int Render::finish_pass(Lane& ln) {
-    const PassDevA& ps = plist[ln.pass];
+    const PassArg& ps = plist[ln.pass];
     const int level = ln.level;
     stt.max_level = std::max(stt.max_level, level);
     int rc;
@@ -3021,7 +3021,7 @@ int Render::run_passes() {
     for (int k = 0; k < lanes; k++) { s->lanes[k].passes.clear(); s->lanes[k].next_pass = 0; }
     for (int p0 = 0; p0 < npix; p0 += np_pass)
         for (int s0 = 0; s0 < total; s0 += ns_chunk) {
-            PassDevA ps = order;
+            PassArg ps = order;
             ps.s0 = tg.s0 + s0; ps.ns = std::min(ns_chunk, total - s0);
             ps.p0 = p0; ps.npass = std::min(np_pass, npix - p0);
             s->lanes[(p0 / np_pass) % lanes].passes.push_back((int)plist.size());
@@ -3137,7 +3137,7 @@ int Render::stream_step(Lane& ln, int m, int g) {
         HIP_TRY(hipMemsetAsync(io.pr.lcnt, 0, sizeof(unsigned) * nLb, ln.st));
     }
     // the step's new camera samples: nodes [m, n) (the wave-uniform shadow walk)
-    io.uni_from = g > 0 ? m : INT_MAX;
+    io.uni_from = g > 0 && !rays ? m : INT_MAX;
     ln.level++;
     return step(ln, seg.F, io);
 }
@@ -3174,7 +3174,7 @@ int Render::run_stream() {
         if ((rc = ln.qcnt.grow(sizeof(unsigned long long) * 128))) return rc;
         if (pt && (rc = ln.lcnt.grow(sizeof(unsigned) * 2 * (size_t)nLb))) return rc;
     }
-    PassDevA& F = seg.F;
+    PassArg& F = seg.F;
     F = order;
     F.s0 = tg.s0; F.ns = total; F.p0 = 0; F.npass = npix;
     const long long all_slots = (long long)npix * total;
@@ -3249,7 +3249,7 @@ int Render::run_stream() {
                     if (ln.step_g[j] > 0) {
                         const int mj = ln.step_m[j];
                         const NodePlanes l0 = {self.col + mj, self.pnt + mj, self.link + mj};
-                        PassDevA P = F;
+                        PassArg P = F;
                         P.p0 = ln.step_gb[j] / total;
                         P.npass = ln.step_g[j] / total;
                         if ((rc = timed_launch(ln, [&] {
@@ -3313,8 +3313,8 @@ void Render::fill_stats(float ms, unsigned nan_queries, const Counters& ctr) {
 }  // namespace
 
 static int render_impl(rtg_scene* s, const rtg_camera_desc* cam, const rtg_render_opts* opts, float* out_dev,
-                       hipStream_t st, const RenderTarget* target = nullptr) {
-    Render r(s, cam);
+                       hipStream_t st, const RenderTarget* target = nullptr, const rtg_ray* rays = nullptr) {
+    Render r(s, cam, rays);
     int rc;
     if ((rc = r.plan(opts, target))) return rc;
     if (!r.tg.acc) { if ((rc = s->d_acc.grow(sizeof(float) * 3 * std::max<size_t>(r.npix, 1)))) return rc; r.tg.acc = s->d_acc.as<float>(); }
@@ -4757,6 +4757,96 @@ int32_t rtg_frame_guides_device(rtg_frame* f, const rtg_frame_guides* out, void*
         HIP_TRY(copy(out->albedo, a.albedo, 3 * n));
         HIP_TRY(copy(out->variance, a.variance, n));
         HIP_TRY(hipStreamSynchronize(st));
+        return RTG_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- rendering caller-supplied primary rays
+// The camera a ray image stands for inside the render: its size, sample count and integrator; the projection
+// fields are never read (the ray passes' kernels load the caller's rays where the others form the camera's).
+static rtg_camera_desc ray_image_camera(const rtg_ray_image* im) {
+    rtg_camera_desc c{};
+    c.gaze[2] = -1.0f; c.up[1] = 1.0f;
+    c.left = -1.0f; c.right = 1.0f; c.bottom = -1.0f; c.top = 1.0f; c.near_distance = 1.0f;
+    c.nx = im->nx; c.ny = im->ny; c.num_samples = im->num_samples;
+    c.integrator = im->integrator; c.pt_flags = im->pt_flags;
+    return c;
+}
+// The checks that need no device, in the documented order; *cam: the stand-in camera, *out_rows: the output's rows.
+static int ray_image_args(const rtg_scene* s, const rtg_ray_image* im, const rtg_ray* rays, const rtg_render_opts* opts,
+                          const float* out, rtg_camera_desc* cam, int* out_rows) {
+    if (!s || !im || !rays || !out) return fail(RTG_ERR_INVALID, "null argument");
+    if (im->nx < 1 || im->ny < 1 || im->num_samples < 1) return fail(RTG_ERR_INVALID, "bad ray image");
+    if (im->pad[0] || im->pad[1] || im->pad[2]) return fail(RTG_ERR_INVALID, "rtg_ray_image.pad must be 0");
+    if (im->integrator != RTG_INTEGRATOR_REFERENCE && im->integrator != RTG_INTEGRATOR_PATH)
+        return fail(RTG_ERR_INVALID, "unknown integrator");
+    if (im->pt_flags & ~(RTG_PT_IMPORTANCE | RTG_PT_NEE | RTG_PT_RUSSIAN_ROULETTE)) return fail(RTG_ERR_INVALID, "unknown pt_flags");
+    *cam = ray_image_camera(im);
+    const rtg_render_opts o = opts ? *opts : rtg_render_opts{};
+    PassDevA order{};                       // the option errors, as Render::plan reports them
+    if (const int rc = pixel_order(o, cam, order)) return rc;
+    if (o.tile_band < 0 || o.segment_pixels < 0 || o.segment_nodes < 0)
+        return fail(RTG_ERR_INVALID, "tile_band / segment_pixels / segment_nodes");
+    if (o.schedule < RTG_SCHEDULE_AUTO || o.schedule > RTG_SCHEDULE_STREAM) return fail(RTG_ERR_INVALID, "schedule");
+    if (o.num_devices > 1 || o.devices) return fail(RTG_ERR_UNSUPPORTED, "rtg_render_rays: the rays live on one device");
+    if (const int nr = scene_ready(s, "host-only scene cannot render")) return nr;
+    *out_rows = o.compact_rows ? order.rows_owned : im->ny;
+    return RTG_OK;
+}
+// Validation, then the render: rays and out on the scene's device.
+static int render_rays_on_device(rtg_scene* s, const rtg_camera_desc* cam, const rtg_ray* rays, const rtg_render_opts* opts,
+                                 float* out_dev, hipStream_t st) {
+    const rtg_render_opts o = opts ? *opts : rtg_render_opts{};
+    PassDevA order{};
+    int rc;
+    if ((rc = pixel_order(o, cam, order))) return rc;
+    if ((rc = s->d_counters.grow(sizeof(unsigned) * 64))) return rc;
+    // (the word is the render's own scratch from here on: render_impl clears the buffer before its first launch)
+    unsigned long long* d_bad = s->d_counters.as<unsigned long long>() + 4;
+    unsigned long long bad = ~0ull;
+    HIP_TRY(hipMemsetAsync(d_bad, 0xFF, sizeof bad, st));
+    launch_check_rays(rays, order.rows_owned, cam->nx, cam->num_samples, order.row_offset, order.row_stride, order.row_block,
+                      d_bad, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad != ~0ull)
+        return fail(RTG_ERR_INVALID, "rtg_render_rays: ray " + std::to_string(bad) + " is not finite or has a zero direction");
+    return render_impl(s, cam, opts, out_dev, st, nullptr, rays);
+}
+
+extern "C" {
+
+int32_t rtg_render_rays_device(rtg_scene* s, const rtg_ray_image* image, const rtg_ray* rays_device, const rtg_render_opts* opts,
+                               float* rgb_out_device, void* stream) {
+    return guarded([&]() -> int32_t {
+        rtg_camera_desc cam;
+        int out_rows = 0;
+        if (const int rc = ray_image_args(s, image, rays_device, opts, rgb_out_device, &cam, &out_rows)) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        return render_rays_on_device(s, &cam, rays_device, opts, rgb_out_device, (hipStream_t)stream);
+    });
+}
+
+int32_t rtg_render_rays(rtg_scene* s, const rtg_ray_image* image, const rtg_ray* rays, const rtg_render_opts* opts, float* rgb_out) {
+    return guarded([&]() -> int32_t {
+        rtg_camera_desc cam;
+        int out_rows = 0;
+        if (const int rc = ray_image_args(s, image, rays, opts, rgb_out, &cam, &out_rows)) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        // staged for the call and released: the rays (28 B each), then the frame
+        const size_t nr = (sizeof(rtg_ray) * (size_t)cam.nx * cam.ny * cam.num_samples + 15) & ~(size_t)15;
+        const size_t nf = sizeof(float) * 3 * (size_t)cam.nx * std::max(out_rows, 1);
+        struct Stage { DBuf d; ~Stage() { d.release(); } } w;
+        int rc = w.d.grow(nr + nf);
+        if (rc) return rc;
+        char* base = w.d.as<char>();
+        HIP_TRY(hipMemcpy(base, rays, sizeof(rtg_ray) * (size_t)cam.nx * cam.ny * cam.num_samples, hipMemcpyHostToDevice));
+        float* d_out = reinterpret_cast<float*>(base + nr);
+        if ((rc = render_rays_on_device(s, &cam, reinterpret_cast<const rtg_ray*>(base), opts, d_out, nullptr))) return rc;
+        if (out_rows > 0) HIP_TRY(hipMemcpy(rgb_out, d_out, sizeof(float) * 3 * (size_t)cam.nx * out_rows, hipMemcpyDeviceToHost));
         return RTG_OK;
     });
 }

@@ -532,6 +532,23 @@ struct PassDevA : PassDev {
     int ord_m = 0, ord_n = 1;
     bool plain() const { return !active && !ord_m; }
 };
+// A pass over caller-supplied primary rays (rtg_render_rays): PassDev plus the caller's array,
+// read in place.  Slot -> pixel and sample as a PassDev; the primary ray of (pixel, sample) is
+// rays[pixel * nsamp + sample] (64-bit index) instead of the camera's.  A third pass type, so that no PassDev /
+// PassDevA instantiation carries the pointer or a branch on it; only the kernels that generate level 0 (GEN)
+// are instantiated for it -- everything else about such a pass is a PassDev's and takes those kernels.
+struct PassDevR : PassDev {
+    const struct ::rtg_ray* rays;
+    int nsamp;
+};
+template <class PS> inline constexpr bool kRayPass = false;
+template <> inline constexpr bool kRayPass<PassDevR> = true;
+// What the host hands the launchers: a PassDevA, or -- rays set -- a ray pass.  Host-side only: with_pass
+// (rtg_device.hip) turns it into the type whose kernels the pass takes.
+struct PassArg : PassDevA {
+    const struct ::rtg_ray* rays = nullptr;
+    int nsamp = 0;
+};
 
 // What one trace -> shade -> shadow step reads and writes: a level of a pass, or a step of the stream
 // schedule (Render::step, rtg_host.cpp).  Each schedule fills it from its own buffers.
@@ -556,7 +573,7 @@ struct StepIO {
     PtRad pr;                     // path tracer
     int uni_from;                 // shadow queries: first camera-sample node (wave-uniform walk), INT_MAX none
 };
-void launch_trace(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+void launch_trace(const SceneView& sv, const CameraDev& cam, const PassArg& ps, uint64_t seed, const StepIO& io,
                   int exhaustive, Counters* ctr, hipStream_t st);
 // queued rays only, full hit records (rtg_trace_closest): no camera, no pass
 void launch_trace_queued(const SceneView& sv, const RayQ rays, HitRec* hits, int n, int exhaustive, hipStream_t st);
@@ -582,9 +599,9 @@ template <bool ANYHIT> __device__ __forceinline__ bool wave_done(const HitRec& h
     else return false;
 }
 #endif
-void launch_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+void launch_shade(const SceneView& sv, const CameraDev& cam, const PassArg& ps, uint64_t seed, const StepIO& io,
                   hipStream_t st);
-void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassDevA& ps, uint64_t seed, const StepIO& io,
+void launch_pt_shade(const SceneView& sv, const CameraDev& cam, const PassArg& ps, uint64_t seed, const StepIO& io,
                      Counters* ctr, hipStream_t st);
 void launch_shadow(const SceneView& sv, const StepIO& io, int exhaustive, Counters* ctr, unsigned* nan_queries,
                    hipStream_t st);
@@ -598,7 +615,7 @@ void launch_resolve_planes(const SceneView& sv, const NodePlanes& self, const No
 // mom (a frame's moments, or null): mean and M2 of each pixel's sample luminance (2 floats per owned
 // pixel, in `acc` order), continued over this launch's samples; mom_k0 = samples they already hold
 void launch_accumulate_planes(const SceneView& sv, const NodePlanes& level0, const NodePlanes& level1, bool resolve,
-                              float* acc, const PassDevA& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
+                              float* acc, const PassArg& ps, int nx, int mode, hipStream_t st, float* mom = nullptr,
                               int mom_k0 = 0);
 void launch_resolve(const SceneView& sv, NodeRec* nodes, const NodeRec* child_nodes, int n, int n_child,
                     hipStream_t st);
@@ -609,7 +626,7 @@ void launch_resolve2(const SceneView& sv, NodeRec* nodes, const NodeRec* child_n
 // level0 / level1 hold NodePlanes over n0 / n1 nodes; whitted: resolve level 0 against level 1
 // level2 (optional): level 1 is resolved inline against it (the bottom-up pass left level 1 unresolved)
 void launch_accumulate(const SceneView& sv, const NodeRec* level0, const NodeRec* level1, bool resolve, float* acc,
-                       const PassDevA& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
+                       const PassArg& ps, int nx, int mode, hipStream_t st, bool whitted, int n0, int n1,
                        const NodeRec* level2 = nullptr, int n2 = 0, float* mom = nullptr, int mom_k0 = 0);
 // A frame's error figures (rtg_frame_error_stats): per-block double partials of the per-pixel mean and
 // standard error (3 doubles per block of 256 pixels in `part`: sum of means, sum of sems, max sem),
@@ -663,6 +680,10 @@ void launch_aov_place(const AovPlanes& in, const AovPlanes& out, int nx, int out
 // rtg_camera_rays: ps is row-major (tile_h = tile_s = 1, no shard); out[i] = the ray of slot i, i < n
 void launch_camera_rays(const CameraDev& cam, const PassDev& ps, uint64_t seed, int n, struct ::rtg_ray* out,
                         hipStream_t st);
+// rtg_render_rays: *bad (device, preset to ~0) = the lowest index of `rays` whose ray is not
+// finite or has a zero direction, over the rays of the shard's owned rows (nx * nsamp records per row)
+void launch_check_rays(const struct ::rtg_ray* rays, int rows_owned, int nx, int nsamp, int row_offset, int row_stride,
+                       int row_block, unsigned long long* bad, hipStream_t st);
 
 // Traversal-tree build records (rtg_host.cpp sah_split, rtg_sah_gpu.hip): one triangle's box and face
 // index (32 B; the centroid is the box centre), and the binned-SAH BVH2 node over a range of them.

@@ -11,3 +11,6 @@ from .scene import Camera, Instance, Light, Material, Object, Scene, Texture, pa
 
 __all__ = ["RtgError", "load_library", "Comm", "Frame", "Renderer", "render_scene", "save_image", "tonemap", "denoise", "Camera", "Instance", "Light",
            "Material", "Object", "Scene", "Texture", "parse_xml", "write_xml", "_abi"]
+from .rays import equirect_rays, ortho_rays
+
+__all__ += ["equirect_rays", "ortho_rays"]

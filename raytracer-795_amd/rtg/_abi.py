@@ -284,6 +284,10 @@ EXPORTS = {
     # ABI 10 additions: updating a built scene in place
     "rtg_scene_update": (C.c_int32, [C.c_void_p, C.POINTER(SceneDesc)]),
     "rtg_scene_top_hash": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    # ABI 10 additions: rendering caller-supplied primary rays
+    "rtg_render_rays": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RenderOpts), C.c_void_p]),
+    "rtg_render_rays_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RenderOpts), C.c_void_p,
+                                           C.c_void_p]),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -340,3 +344,9 @@ def check(rc: int, lib=None):
         lib = lib or _lib
         msg = lib.rtg_last_error().decode() if lib is not None else ""
         raise RtgError(f"{STATUS.get(rc, rc)}: {msg}")
+
+
+class RayImage(C.Structure):
+    """rtg_ray_image (32 bytes): the image caller-supplied rays are laid over (rtg_render_rays)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("num_samples", C.c_int32), ("integrator", C.c_int32),
+                ("pt_flags", C.c_int32), ("pad", C.c_int32 * 3)]

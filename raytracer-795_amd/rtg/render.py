@@ -685,3 +685,48 @@ Renderer.top_hash = _renderer_top_hash
 Renderer.occluded = _renderer_occluded
 Renderer.trace_device = _renderer_trace_device
 Renderer.occluded_device = _renderer_occluded_device
+
+
+# ---------------------------------------------------------------------------- caller-supplied primary rays
+def _ray_image(nx: int, ny: int, num_samples: int, integrator: int, pt_flags: int):
+    return A.RayImage(int(nx), int(ny), int(num_samples), int(integrator), int(pt_flags))
+
+
+def _renderer_render_rays(self, origins, directions, times=None, integrator: int = 0, pt_flags: int = 0, **kw) -> np.ndarray:
+    """Render caller-supplied primary rays (rtg_render_rays): `origins` and `directions` (ny, nx, ns, 3), `times`
+    (ny, nx, ns) or None (0) -- the shapes camera_rays returns; sample s of pixel (x, y) at [y, x, s].  The
+    integrator (0 the reference's, 1 the path tracer with `pt_flags`) runs over them with everything below
+    level 0 as render() has it for a camera of that size and sample count: a camera's own rays under the same
+    seed give render()'s bits.  Directions are used as given (supply unit vectors).  `kw`: the render options;
+    returns (rows, nx, 3) float32 as render()."""
+    o = np.asarray(origins, np.float32)
+    d = np.asarray(directions, np.float32)
+    if o.ndim != 4 or o.shape[3] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both be (ny, nx, ns, 3)")
+    ny, nx, ns = o.shape[:3]
+    t = np.zeros((ny, nx, ns), np.float32) if times is None else np.asarray(times, np.float32)
+    if t.shape != (ny, nx, ns):
+        raise ValueError("times must be (ny, nx, ns)")
+    rays = np.empty((ny, nx, ns, 7), np.float32)
+    rays[..., 0:3], rays[..., 3:6], rays[..., 6] = o, d, t
+    opt = self.opts(**kw)
+    rows = (self.lib.rtg_shard_rows(ny, opt.row_offset, opt.row_stride, opt.row_block) if opt.compact_rows else ny)
+    out = np.empty((rows, nx, 3), np.float32)
+    im = _ray_image(nx, ny, ns, integrator, pt_flags)
+    A.check(self.lib.rtg_render_rays(self.handle, C.byref(im), rays.ctypes.data, C.byref(opt), out.ctypes.data), self.lib)
+    return out
+
+
+def _renderer_render_rays_device(self, rays_ptr: int, nx: int, ny: int, num_samples: int, out_ptr: int, stream: int = 0,
+                                 integrator: int = 0, pt_flags: int = 0, **kw):
+    """render_rays() on caller-owned device arrays (rtg_render_rays_device), enqueued on `stream`, synchronous
+    on return: rays a contiguous float32 (ny * nx * num_samples, 7) tensor as for trace_device, read in place;
+    out a float32 (rows, nx, 3) tensor; pass their data_ptr()."""
+    im = _ray_image(nx, ny, num_samples, integrator, pt_flags)
+    opt = self.opts(**kw)
+    A.check(self.lib.rtg_render_rays_device(self.handle, C.byref(im), C.c_void_p(rays_ptr or None), C.byref(opt),
+                                            C.c_void_p(out_ptr or None), C.c_void_p(stream)), self.lib)
+
+
+Renderer.render_rays = _renderer_render_rays
+Renderer.render_rays_device = _renderer_render_rays_device
